@@ -1,7 +1,7 @@
 """Benchmark: activations/sec of the full crosscoder training step (fwd + bwd + clip + Adam).
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--config C] [--batch B] [--n-models n]
-                  [--d-model d] [--dict-size h] [--no-cpu-baseline]
+                  [--d-model d] [--dict-size h] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
 
 Workloads are BASELINE.json's configs (synthetic normalised activations, reference init seed 49, bf16):
   config 2  CrossCoder 2x2304->16384, batch 4096          -- the default at N = 1 (the metric's config)
@@ -19,11 +19,17 @@ config 3 (2^17 latents, as BASELINE.json's north_star asks), whose rows cost 8x 
 restates the throughput in config-2 rows of equal FLOP (10.n.d.h FLOP of step work per row).
 `latent_acts_per_s` = value x dict_size.
 
-The JSON line also carries `roofline` (dominant kernel's achieved TFLOP/s from HIP events around its
-launches inside the timed region, vs the bf16 dense MFMA peak), `hbm` (achieved GB/s of the
-streaming kernels: Adam halves, input prep -- and the loss kernel where G2 does not carry the loss in its
-epilogue -- from an untimed attribution pass) and `cpu_baseline` (the oracle CPU step timed on this host,
-rank 0, N = 1 only).
+A plain run sets up, warms up, times the `--steps` steps and prints the line: the headline figures (`value`,
+`ms_per_step` = milliseconds per timed step), the workload, the shader clock of the timed region and the last
+step's losses.  `--dump-outputs DIR` then writes what the last timed step left its caller -- the loss dict and the
+updated parameters (rank 0's shard when latent-sharded) -- as float32 / float64 DIR/<name>.npy (dump_outputs);
+the inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
+`--full` adds what takes runs of its own: `kernels_ms` and `hbm` (achieved GB/s of the streaming kernels: Adam
+halves, input prep -- and the loss kernel where G2 does not carry the loss in its epilogue) from an untimed
+attribution pass before the timed region, `roofline` (dominant kernel's achieved TFLOP/s from HIP events
+around its launches inside the timed region, vs the bf16 dense MFMA peak), `cpu_baseline` (the oracle CPU step
+timed on this host, rank 0, N = 1 only), and at N > 1 `n1_same_workload` and the exchange's exposed time.
 """
 import argparse
 import datetime
@@ -356,6 +362,59 @@ def hbm_rows(kern, B, n, d, h_local, es=2):
     return out
 
 
+def roofline_report(timer, dom, B, K, h_local, metric_config):
+    """--full: the dominant kernel `dom` against the bf16 MFMA peak, from the event samples `timer` took around its
+    launches inside the timed region; `metric_config` (config 2 on one GPU) adds the committed profiles' figures."""
+    dom_ms = timer.averages_ms()[dom]
+    samples = sorted(s_.elapsed_time(e_) for s_, e_ in timer.rec.get(dom, []))
+    gemm_flop = 2.0 * B * K * h_local  # per GEMM (per rank)
+    # G4G5_wgrad is one launch computing both weight gradients (cc_wgrad_both)
+    dom_flop = gemm_flop * (2 if dom == "G4G5_wgrad" else 1)
+    achieved = dom_flop / (dom_ms * 1e-3) / 1e12
+    if not engine.transposed_wgrad(B, K, h_local, torch.bfloat16):  # batch-major MN/MN form (cc_wgrad_both)
+        SPAN_KERNEL["G4G5_wgrad"] = "gemm_pp_dual_kernel<false, false, 4, 5>"
+    traffic, traffic_src = pmc_traffic(dom) if metric_config else (None, None)
+    # algorithmic operand/output bytes of the dominant launch (each input read once, output written once)
+    es = 2  # bf16
+    alg = {"G1_encode": (B * K + h_local * K + 2 * B * h_local) * es,
+           "G2_decode": (B * h_local + h_local * K + 3 * B * K) * es,  # + x in, g_recon / g_recon^T out (fused loss)
+           "G3_dacts": (B * K + h_local * K + B * h_local) * es + B * h_local // 8,  # (+ G1's mask bits, g_pre^T out)
+           "G4G5_wgrad": (2 * B * h_local + 2 * B * K + 3 * h_local * K) * es}
+    return {"bound": "mfma", "kernel": dom, "kernel_name": SPAN_KERNEL.get(dom), "kernel_ms": round(dom_ms, 4),
+            "kernel_samples": len(samples),
+            "kernel_ms_min_med_max": [round(samples[0], 4), round(samples[len(samples) // 2], 4),
+                                      round(samples[-1], 4)] if samples else None,
+            "rocprof": rocprof_average(dom) if metric_config else None,
+            "achieved": round(achieved, 1),
+            "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
+            "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": traffic_src,
+            "algorithmic_bytes": alg.get(dom)}
+
+
+LOSS_KEYS = ("loss", "l2_loss", "l1_loss", "l0_loss", "l1_coeff", "lr", "explained_variance",
+             "explained_variance_A", "explained_variance_B")
+DUMP_SAMPLE = 1 << 20  # elements written of each parameter (all of it when it has no more): 4 MiB as float32
+
+
+def dump_outputs(out_dir, tr, last):
+    """--dump-outputs: what the last timed step left its caller.  losses.npy: step()'s loss dict in LOSS_KEYS order
+    (float64); W_enc / W_dec / b_enc / b_dec .npy: the parameters after that step's Adam update (float32,
+    flattened; of a parameter above DUMP_SAMPLE elements the elements at DUMP_SAMPLE indices drawn once from a
+    generator seeded with 0, the same in every run of the same shape)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "losses.npy"), np.array([last[k] for k in LOSS_KEYS], dtype=np.float64))
+    tr.synchronize()
+    sd = tr.crosscoder.state_dict()
+    g = torch.Generator().manual_seed(0)
+    for name in ("W_enc", "W_dec", "b_enc", "b_dec"):
+        v = sd[name].detach().reshape(-1)
+        if v.numel() > DUMP_SAMPLE:
+            v = v[torch.randint(v.numel(), (DUMP_SAMPLE,), generator=g).to(v.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), v.float().cpu().numpy())
+
+
 def free_port():
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -460,12 +519,18 @@ def main():
     ap.add_argument("--n-models", type=int)
     ap.add_argument("--d-model", type=int)
     ap.add_argument("--dict-size", type=int, help="the WHOLE dictionary (split over the ranks when N > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: per-kernel attribution pass (kernels_ms, hbm), live "
+                         "roofline samples in the timed region, the CPU baseline (N = 1), n1_same_workload (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU oracle's timing")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the last step's losses and the updated parameters as "
+                         "DIR/<name>.npy (float32 / float64; seeded samples of the large ones)")
     ap.add_argument("--comm", choices=("auto", "all_reduce", "reduce_scatter"), default=None,
                     help="latent-sharded step: the partial-reconstruction exchange (default N > 1: auto = time both "
                          "during warm-up, run the faster; one rank: all_reduce)")
     ap.add_argument("--no-n1", action="store_true",
-                    help="N > 1: skip the in-job one-GPU measurement of the same workload (n1_same_workload)")
+                    help="--full at N > 1: skip the in-job one-GPU measurement of the same workload (n1_same_workload)")
     ap.add_argument("--recon-chunks", type=int, default=None,
                     help="latent-sharded step: batch slices the all-reduce is overlapped by (default N > 1: timed "
                          "in warm-up with --comm auto, 1 / 2 / 4; one rank: 1)")
@@ -474,6 +539,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # no torchrun wrapper: this process becomes the launcher of the N ranks
@@ -539,7 +606,7 @@ def run_rank(args):
         from crosscoder_amd import sharded
 
         n1 = None
-        if world > 1 and not args.no_n1:
+        if world > 1 and args.full and not args.no_n1:
             # the strong-scaling curve's own 1-GPU point, measured in this job before the sharded trainer exists
             if rank == 0:
                 n1 = n1_same_workload(cfg)
@@ -554,20 +621,22 @@ def run_rank(args):
     for _ in range(args.warmup):
         tr.step()
     exchange = measure_exchange(tr, comm, K, slices=args.recon_chunks) if sharded_path else None
-    # attribution pass (not timed): every kernel bracketed by events
-    attrib = EventTimer()
-    engine.TIMER = attrib
-    attrib.enabled = True
-    for _ in range(max(3, min(args.steps, 10))):
-        tr.step()
-    torch.cuda.synchronize()
-    kern = attrib.averages_ms()
-    if exchange is not None:
-        exchange_exposed(kern, exchange)
-    gemms = {k: v for k, v in kern.items() if k.startswith("G")}
-    dom = max(gemms, key=gemms.get)
-    engine.TIMER = timer
-    timer.only = dom  # the roofline kernel, measured live inside the timed region
+    kern = dom = None
+    if args.full:
+        # attribution pass (not timed): every kernel bracketed by events
+        attrib = EventTimer()
+        engine.TIMER = attrib
+        attrib.enabled = True
+        for _ in range(max(3, min(args.steps, 10))):
+            tr.step()
+        torch.cuda.synchronize()
+        kern = attrib.averages_ms()
+        if exchange is not None:
+            exchange_exposed(kern, exchange)
+        gemms = {k: v for k, v in kern.items() if k.startswith("G")}
+        dom = max(gemms, key=gemms.get)
+        engine.TIMER = timer
+        timer.only = dom  # the roofline kernel, measured live inside the timed region
     clk = clock_words(tr)
     if clk is not None:
         clk.zero_()
@@ -578,7 +647,7 @@ def run_rank(args):
     for i in range(args.steps):
         # the roofline launch is bracketed on every SPAN_EVERY-th timed step (each event record
         # idles the stream ~6 us, tools/event_cost.py: sampling keeps that out of most steps)
-        timer.enabled = i % SPAN_EVERY == 0
+        timer.enabled = args.full and i % SPAN_EVERY == 0
         last = tr.step()
     torch.cuda.synchronize()
     if sharded_path:
@@ -596,23 +665,7 @@ def run_rank(args):
     rows_per_s = B / step_s  # activations (batch rows) trained per second by the whole job: `value`
     # config-2 rows of equal step work (10.n.d.h FLOP per row): config 2 counts 1, config 3 (2^17 latents) 8
     per_row = (n * d * h_total) / (2 * 2304 * 16384)
-    dom_ms = timer.averages_ms()[dom]
-    samples = sorted(s_.elapsed_time(e_) for s_, e_ in timer.rec.get(dom, []))
-    gemm_flop = 2.0 * B * K * h_local  # per GEMM (per rank)
-    # G4G5_wgrad is one launch computing both weight gradients (cc_wgrad_both)
-    dom_flop = gemm_flop * (2 if dom == "G4G5_wgrad" else 1)
-    achieved = dom_flop / (dom_ms * 1e-3) / 1e12
     step_flop = 5 * 2.0 * B * K * h_total  # whole job
-    if not engine.transposed_wgrad(B, K, h_local, torch.bfloat16):  # batch-major MN/MN form (cc_wgrad_both)
-        SPAN_KERNEL["G4G5_wgrad"] = "gemm_pp_dual_kernel<false, false, 4, 5>"
-    traffic, traffic_src = pmc_traffic(dom) if (config, world, custom) == (2, 1, False) else (None, None)
-    # algorithmic operand/output bytes of the dominant launch (each input read once, output written once)
-    es = 2  # bf16
-    alg = {"G1_encode": (B * K + h_local * K + 2 * B * h_local) * es,
-           "G2_decode": (B * h_local + h_local * K + 3 * B * K) * es,  # + x in, g_recon / g_recon^T out (fused loss)
-           "G3_dacts": (B * K + h_local * K + B * h_local) * es + B * h_local // 8,  # (+ G1's mask bits, g_pre^T out)
-           "G4G5_wgrad": (2 * B * h_local + 2 * B * K + 3 * h_local * K) * es}
-    dom_alg_bytes = alg.get(dom)
     name = f"{n}x{d}->{h_total}"
     result = {
         "metric": "activations/sec per train step (fwd+bwd+Adam), 2x2304->16384; % bf16 MFMA peak",
@@ -641,31 +694,27 @@ def run_rank(args):
         "metric_equiv_acts_per_s": round(rows_per_s * per_row, 1),
         "metric_equiv_per_row": per_row,
         "latent_acts_per_s": round(rows_per_s * h_total, 1),
-        # N > 1: the same workload on one GPU, measured in this job on rank 0 before the sharded run, so the
-        # strong-scaling curve has its own 1-GPU point (the driver's N = 1 run is the metric's config 2, a
-        # different dictionary): efficiency = value / (N x n1_same_workload.value)
-        "n1_same_workload": n1 if world > 1 else None,
         "exchange": exchange,
         "step_mfma_frac": round(step_flop / step_s / 1e12 / (PEAK_BF16_TFLOPS * world), 4),
-        "kernels_ms": {k: round(v, 4) for k, v in sorted(kern.items())},
-        "roofline": {"bound": "mfma", "kernel": dom, "kernel_name": SPAN_KERNEL.get(dom), "kernel_ms": round(dom_ms, 4),
-                     "kernel_samples": len(samples),
-                     "kernel_ms_min_med_max": [round(samples[0], 4), round(samples[len(samples) // 2], 4),
-                                               round(samples[-1], 4)] if samples else None,
-                     "rocprof": rocprof_average(dom) if (config, world, custom) == (2, 1, False) else None,
-                     "achieved": round(achieved, 1),
-                     "peak": round(PEAK_BF16_TFLOPS, 1), "unit": "TFLOP/s", "frac": round(achieved / PEAK_BF16_TFLOPS, 4),
-                     "traffic": traffic, "traffic_unit": "HBM bytes per launch (PMC)", "traffic_source": traffic_src,
-                     "algorithmic_bytes": dom_alg_bytes},
         # the shader clock over the timed region's roofline launches (DVFS under the package power cap: the same
-        # build runs faster on a box that holds a higher clock, so round-over-round comparisons need it)
+        # build runs faster on a machine that holds a higher clock, so comparisons between runs need it)
         "effective_sclk_ghz": clock["effective_sclk_ghz"] if clock else None,
         "clock": clock,
-        "hbm": hbm_rows(kern, B, n, d, h_local),
         "last_loss": {k: round(v, 6) for k, v in last.items()},
+        "full": args.full,
     }
+    if args.full:
+        # N > 1: the same workload on one GPU, measured in this job on rank 0 before the sharded run, so the
+        # strong-scaling curve has its own 1-GPU point (the default N = 1 run is the metric's config 2, a
+        # different dictionary): efficiency = value / (N x n1_same_workload.value)
+        result["n1_same_workload"] = n1 if world > 1 else None
+        result["kernels_ms"] = {k: round(v, 4) for k, v in sorted(kern.items())}
+        result["roofline"] = roofline_report(timer, dom, B, K, h_local, (config, world, custom) == (2, 1, False))
+        result["hbm"] = hbm_rows(kern, B, n, d, h_local)
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, tr, last)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             result["cpu_baseline"] = cpu_baseline(B, n, d, h_total)
         print(json.dumps(result), flush=True)
     if sharded_path:

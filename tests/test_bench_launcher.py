@@ -1,7 +1,8 @@
 """bench.py's N-rank entry, on the CPU: `--gpus N` without a torchrun wrapper starts the N
 ranks itself and relays rank 0's line, refuses to run with fewer GPUs than asked, and kills ranks that pass its
 deadline.  The rank bodies here are the gloo `--launcher-check` (no GPU, no HIP library); the GPU rehearsal of
-the real step (`CC_BENCH_ONE_DEVICE=1 python bench.py --gpus 2`) is in tests/test_gpu_sharded.py."""
+the real step (`CC_BENCH_ONE_DEVICE=1 python bench.py --gpus 2`) is in tests/test_gpu_sharded.py.  Also here: the
+host logic of `--dump-outputs`, and one plain single-GPU run (small shapes) with its dump."""
 import json
 import os
 import subprocess
@@ -92,6 +93,76 @@ def _load_bench():
     bench = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(bench)
     return bench
+
+
+def test_dump_outputs_writes_losses_and_seeded_parameter_samples(tmp_path):
+    """bench.py --dump-outputs, its host logic: losses.npy is the step's loss dict in LOSS_KEYS order (float64); each
+    parameter is written flattened as float32, whole when it has at most DUMP_SAMPLE elements, else the elements at
+    DUMP_SAMPLE seeded indices -- the same ones in every call."""
+    import numpy as np
+    import torch
+
+    bench = _load_bench()
+    bench.DUMP_SAMPLE = 64
+    sd = {"W_enc": torch.arange(2 * 8 * 32, dtype=torch.float32).reshape(2, 8, 32).to(torch.bfloat16),
+          "W_dec": -torch.arange(32 * 2 * 8, dtype=torch.float32).reshape(32, 2, 8).to(torch.bfloat16),
+          "b_enc": torch.linspace(0, 1, 32).to(torch.bfloat16), "b_dec": torch.ones(2, 8, dtype=torch.bfloat16)}
+    calls = []
+    tr = type("T", (), {"synchronize": lambda self: calls.append("sync")})()
+    tr.crosscoder = type("C", (), {"state_dict": lambda self: dict(sd)})()
+    last = {k: 0.5 + i for i, k in enumerate(bench.LOSS_KEYS)}
+    out = [tmp_path / "a", tmp_path / "b" / "nested"]
+    for o in out:
+        bench.dump_outputs(str(o), tr, last)
+    assert calls == ["sync", "sync"]
+    got = [{f[:-4]: np.load(o / f) for f in sorted(os.listdir(o))} for o in out]
+    assert sorted(got[0]) == ["W_dec", "W_enc", "b_dec", "b_enc", "losses"]
+    for k, v in got[0].items():
+        assert v.dtype == (np.float64 if k == "losses" else np.float32) and v.ndim == 1, k
+        assert np.array_equal(v, got[1][k]), k
+    assert got[0]["losses"].tolist() == [0.5 + i for i in range(9)]
+    assert np.array_equal(got[0]["b_enc"], sd["b_enc"].float().numpy())
+    assert np.array_equal(got[0]["b_dec"], np.ones(16, dtype=np.float32))
+    for k in ("W_enc", "W_dec"):  # 512 elements: sampled; every value names its own index (exact in bf16 below 256,
+        flat = sd[k].float().reshape(-1).numpy()  # so compare by membership and count)
+        assert got[0][k].shape == (64,) and np.isin(got[0][k], flat).all()
+        assert len(np.unique(got[0][k])) > 16
+    assert not np.array_equal(np.abs(got[0]["W_enc"]), np.abs(got[0]["W_dec"]))  # (one generator, drawn in order)
+
+
+def test_plain_and_full_options_parse():
+    """`--full` and `--dump-outputs DIR` exist and default to off; a run with no timed step is refused."""
+    p, _ = run(["--steps", "0"])
+    assert p.returncode == 2 and "--steps" in p.stderr
+    p, _ = run(["--help"])
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs DIR" in p.stdout
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_line_and_dumps_its_outputs(gpu, tmp_path):
+    """A plain `bench.py --gpus 1` run (small shapes) prints one line with the headline fields and none of the
+    `--full` measurements, and `--dump-outputs` writes the last timed step's losses and the updated parameters."""
+    import numpy as np
+
+    out = tmp_path / "dump"
+    p, _ = run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "256", "--d-model", "64", "--dict-size",
+                "512", "--dump-outputs", str(out)])
+    assert p.returncode == 0, p.stderr[-3000:]
+    (line,) = json_lines(p.stdout)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["unit"] == "activations/s" and line["higher_is_better"] is True and line["dtype"] == "bf16"
+    # (ms_per_step is rounded to 1e-4 ms: under 0.5 % of any step above 0.02 ms)
+    assert line["ms_per_step"] > 0.02 and line["value"] == pytest.approx(256 / (line["ms_per_step"] * 1e-3), rel=5e-3)
+    assert not {"kernels_ms", "roofline", "hbm", "cpu_baseline", "n1_same_workload"} & set(line)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert {k: v.shape for k, v in got.items()} == {"losses": (9,), "W_enc": (2 * 64 * 512,), "W_dec": (512 * 2 * 64,),
+                                                    "b_enc": (512,), "b_dec": (2 * 64,)}
+    bench = _load_bench()
+    for v, k in zip(got["losses"], bench.LOSS_KEYS):
+        assert v == pytest.approx(line["last_loss"][k], abs=1e-6), k
+    for k, v in got.items():
+        assert v.dtype == (np.float64 if k == "losses" else np.float32) and np.isfinite(v).all(), k
+    assert np.abs(got["b_enc"]).max() > 0  # (b_enc starts at zero: the dump is taken after the Adam updates)
 
 
 class _FakeShardedTrainer:

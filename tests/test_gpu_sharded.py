@@ -116,8 +116,8 @@ def test_bench_gpus2_rehearsal_launches_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(CC_BENCH_ONE_DEVICE="1", PYTHONDONTWRITEBYTECODE="1")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--config", "2", "--steps", "2",
-                        "--warmup", "1", "--no-cpu-baseline", "--deadline", "200"], capture_output=True, text=True,
-                       env=env, timeout=260, cwd=root)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--deadline", "200"], capture_output=True,
+                       text=True, env=env, timeout=260, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     (line,) = [json.loads(s) for s in p.stdout.splitlines() if s.startswith("{")]
     assert line["n_gpus"] == 2 and line["world_size_pg"] == 2 and line["pg_backend"] == "gloo"

@@ -33,14 +33,14 @@ for s in $STEPS; do
   case $s in
     test) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread ;;
     smoke) run smoke 200 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python bench.py ;;
-    configs) for c in 3 4 5; do run bench_config$c 400 python bench.py --config $c --no-cpu-baseline --steps 10 --warmup 3; done ;;
-    rehearse) for n in 2 4; do CC_BENCH_ONE_DEVICE=1 run rehearse_n$n 400 python bench.py --gpus $n --steps 5 \
+    bench) run bench 400 python bench.py --full ;;
+    configs) for c in 3 4 5; do run bench_config$c 400 python bench.py --full --config $c --no-cpu-baseline --steps 10 --warmup 3; done ;;
+    rehearse) for n in 2 4; do CC_BENCH_ONE_DEVICE=1 run rehearse_n$n 400 python bench.py --full --gpus $n --steps 5 \
                 --warmup 2 --deadline 360 --no-cpu-baseline; done ;;
-    sharded) run bench_sharded 300 python bench.py --no-cpu-baseline --force-sharded
-             run bench_sharded_rs 300 python bench.py --no-cpu-baseline --force-sharded --comm reduce_scatter ;;
+    sharded) run bench_sharded 300 python bench.py --full --no-cpu-baseline --force-sharded
+             run bench_sharded_rs 300 python bench.py --full --no-cpu-baseline --force-sharded --comm reduce_scatter ;;
     prof) run rocprof_stats 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof" -o run -- \
-            python bench.py --no-cpu-baseline ;;
+            python bench.py --full --no-cpu-baseline ;;
     gemm) run gemm_bench 300 python tools/gemm_bench.py crosscoder-model-diff-replication_amd/libcrosscoder_hip.so ;;
     ab) run gemm_ab 400 python tools/gemm_bench.py crosscoder-model-diff-replication_amd/exp/base.so \
           crosscoder-model-diff-replication_amd/libcrosscoder_hip.so ;;
