@@ -571,3 +571,34 @@ def decoder_stats(W_dec_hk, n, d):
     check(lib().cc_decoder_stats(_ptr(W_dec_hk), h, n, d, dtype_code(W_dec_hk.dtype), _ptr(norms), _ptr(rel),
                                  _ptr(cos), _stream(W_dec_hk)))
     return norms, rel, cos
+
+
+# ---------------------------------------------------------------- latent statistics (latent_stats.py)
+def latent_stats_max_k():
+    return int(lib().cc_latent_stats_max_k())
+
+
+def latent_stats_update(acts, h, k, count, sum_, hist, topk_val, topk_row, row_ids=None, row0=0):
+    """One pass over acts [B, ld >= h] (rows contiguous) folded into the state tensors for latents 0..h-1:
+    count [h] int64, sum_ [h] fp32, hist [h, 32] int64 or None, topk_val [h, k] fp32, topk_row [h, k] int64
+    (cc_latent_stats_update; fresh state: zeros, topk_row -1).  Row b has id row_ids[b] (int64 [B] on the
+    device) or row0 + b."""
+    if acts.dim() != 2 or acts.stride(1) != 1:
+        raise ValueError("acts must be [rows, width] with contiguous rows")
+    # (a one-row view may carry any stride: keep it where it is a row pitch)
+    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    dev = acts.device
+    for name, t, dt, shape in (("count", count, torch.int64, (h,)), ("sum", sum_, torch.float32, (h,)),
+                               ("hist", hist, torch.int64, (h, 32)), ("topk_val", topk_val, torch.float32, (h, k)),
+                               ("topk_row", topk_row, torch.int64, (h, k))):
+        if t is None and name == "hist":
+            continue
+        if t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    if row_ids is not None:
+        if row_ids.dtype != torch.int64 or row_ids.device != dev or tuple(row_ids.shape) != (B,):
+            raise ValueError(f"row_ids must be an int64 tensor of shape ({B},) on {dev}")
+        row_ids = row_ids.contiguous()
+    check(lib().cc_latent_stats_update(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(row_ids), int(row0), int(k),
+                                       _ptr(count), _ptr(sum_), _ptr(hist), _ptr(topk_val), _ptr(topk_row),
+                                       _stream(acts)))

@@ -75,7 +75,13 @@ class LambdaLRHost:
 
 
 class Trainer:
-    def __init__(self, cfg, model_A=None, model_B=None, all_tokens=None, buffer=None, crosscoder=None, logger=None):
+    def __init__(self, cfg, model_A=None, model_B=None, all_tokens=None, buffer=None, crosscoder=None, logger=None,
+                 latent_stats=None):
+        """latent_stats (framework extension): a LatentStats of this trainer's crosscoder; every step then folds
+        its activations into it (one launch after the forward -- G1, G2 and the loss rows -- and before G3, on the same
+        stream; row ids step * batch_size + b).  The step's own launches are
+        the same with and without it; read `trainer.latent_stats.result()`, e.g. in `logger`.  bf16 crosscoders only:
+        the fp32 step's streams are not shown to be independent of what else is launched."""
         self.cfg = cfg
         self.model_A = model_A
         self.model_B = model_B
@@ -86,6 +92,13 @@ class Trainer:
         self.scheduler = LambdaLRHost(self.optimizer, self.lr_lambda)
         self.step_counter = 0
         self.logger = logger
+        if latent_stats is not None and latent_stats.cc is not self.crosscoder:
+            raise ValueError("latent_stats must be built on this trainer's crosscoder")
+        if latent_stats is not None and self.crosscoder.dtype != torch.bfloat16:
+            raise ValueError("Trainer(latent_stats=...) serves enc_dtype 'bf16' only: a reader of the fp32 step's "
+                             "decoder half is not reliably ordered after its side-stream Adam (DESIGN.md section 3.7); "
+                             "call LatentStats.update on the batches instead")
+        self.latent_stats = latent_stats
         self._mapped = None  # mapped host words the step's loss tail writes (allocated on the first step)
         self._seq = 0
         self._side = None  # stream of the decoder half's Adam (created on the first step)
@@ -115,6 +128,8 @@ class Trainer:
         side = self._side_stream()
         # prep, G1, G2 + the loss rows (one pass where decode_loss_t serves the shape)
         engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False)
+        if self.latent_stats is not None:  # (after G2 and the loss rows, before G3; acts is only read from G1 on: this stream's order suffices)
+            self.latent_stats.update_from_acts(ws.acts, row0=self.step_counter * self.cfg["batch_size"])
         # the loss scalars: into mapped host memory from the G3 launch (or, where G3 cannot carry the tail, from a
         # launch on the side stream beside G3)
         engine.loss_finalize_with_g3(ws, side, host=host, seq=seq)

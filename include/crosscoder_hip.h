@@ -469,6 +469,25 @@ int cc_fold_scaling(void* W_enc, void* W_dec, void* b_dec, const float* scale, i
 int cc_decoder_stats(const void* W_dec, int64_t h, int64_t n, int64_t d, int dtype, float* norms, float* relative,
                      float* cosine, void* stream);
 
+/* Per-latent activation statistics (the notebook's latent dashboards), one pass over acts [B][ld]
+ * (h <= ld, ld even; the layout cc_encode_fwd and the step write; acts aligned to one
+ * column pair: 4 bytes bf16, 8 bytes fp32), folded into
+ * caller-owned state for latents 0..h-1 that persists across calls.  Only elements > 0 take part
+ * (negative pre-activations and NaN are ignored).
+ *   count[h] (int64) += rows with a positive value;  sum[h] (fp32) += the batch's fp32 sum of them (a
+ *   summation order fixed by (B, h) and by whether k <= 4);  hist[h][32] (int64, optional) += a log2 histogram, bin =
+ *   clamp(floor(log2 v) + 16, 0, 31) from the exponent field;  topk_val[h][k] (fp32) / topk_row[h][k] (int64),
+ *   1 <= k <= cc_latent_stats_max_k(): the k largest values seen so far with their row ids, sorted by value
+ *   descending, ties by row id ascending -- exactly the first k of all candidates sorted that way, in
+ *   whatever order the batches arrive; unused slots are (0, -1), which is also the initial state (count,
+ *   sum and hist start at 0).  Row b of the batch has id row_ids[b] (int64 [B]) if row_ids != NULL, else
+ *   row0 + b.  No global atomics; results are bit-reproducible.
+ * CC_ERR_SHAPE: k out of range, ld < h, ld odd, B < 1, h < 1. */
+int cc_latent_stats_max_k(void);
+int cc_latent_stats_update(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const int64_t* row_ids,
+                           int64_t row0, int k, int64_t* count, float* sum, int64_t* hist, float* topk_val,
+                           int64_t* topk_row, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
