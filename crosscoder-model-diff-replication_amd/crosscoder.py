@@ -58,6 +58,24 @@ def write_checkpoint(state_dict, cfg, save_dir=None, version=0):
     return save_dir, version + 1
 
 
+ACTIVATIONS = ("relu", "topk")
+
+
+def activation_of(cfg):
+    """(activation, k) of a cfg (framework extension; the keys travel in the checkpoint's cfg json): "relu", the
+    reference's and the default, or "topk" -- each row keeps its cfg["k"] largest positive pre-activations
+    (ties: the smaller latent), the rest are zero -- which needs cfg["k"], an int in 1..dict_size."""
+    act = cfg.get("activation", "relu")
+    if act not in ACTIVATIONS:
+        raise ValueError(f"cfg['activation'] must be one of {ACTIVATIONS}, got {act!r}")
+    if act == "relu":
+        return act, None
+    k = cfg.get("k")
+    if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= cfg["dict_size"]:
+        raise ValueError(f"activation 'topk' needs cfg['k'], an int in 1..dict_size ({cfg['dict_size']}), got {k!r}")
+    return act, k
+
+
 class CrossCoder(nn.Module):
     def __init__(self, cfg, n_models: Optional[int] = None, init_W_dec: Optional[torch.Tensor] = None):
         """init_W_dec (framework extension): start from this decoder ([h, n, d], W_enc = its rearranged
@@ -66,6 +84,7 @@ class CrossCoder(nn.Module):
         super().__init__()
         self.cfg = cfg
         d_hidden = cfg["dict_size"]
+        self.activation, self.k = activation_of(cfg)
         d_in = cfg["d_in"]
         self.n_models = int(n_models if n_models is not None else cfg.get("n_models", 2))
         self.dtype = DTYPES[cfg["enc_dtype"]]
@@ -155,7 +174,7 @@ class CrossCoder(nn.Module):
         ws = self._ws
         if (ws is None or ws.B != B or ws.x.device != a.data.device
                 or (ws.busy is not None and ws.busy() is not None)):
-            ws = engine.StepWorkspace(B, self.n_models, self._dp, self._hp, self.dtype, a.data.device)
+            ws = engine.StepWorkspace(B, self.n_models, self._dp, self._hp, self.dtype, a.data.device, topk=self.k)
             self._ws = ws
         return ws
 
@@ -181,7 +200,32 @@ class CrossCoder(nn.Module):
         xf = self._flat_x(x)
         acts = torch.empty(xf.shape[0], self._hp, dtype=self.dtype, device=xf.device)
         ops.encode_fwd(xf, a.W_enc_hk, a.b_enc, acts, apply_relu)
+        if self.k is not None and apply_relu:  # TopK: each row's k largest positive values (the padding latents are 0)
+            ops.topk_rows(acts, self._hp, self.k, out=acts)
         return acts[:, :self.d_hidden].contiguous() if self._hp != self.d_hidden else acts
+
+    ENCODE_ROWS = 4096  # rows encode_topk encodes per launch pair (its one activation buffer)
+
+    def encode_topk(self, x, k=None):
+        """x [rows, n_models, d_model] -> (values [rows, k], indices [rows, k] int32): each row's k largest positive
+        activations of relu(x W_enc + b_enc) (ties: the smaller latent) in ascending latent index, padded with
+        (0, -1) where fewer are positive -- the compact form of a wide dictionary's activations.  Framework
+        extension; serves any crosscoder (k defaults to cfg["k"]); indices refer to the dict_size latents."""
+        k = self.k if k is None else k
+        if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= self.d_hidden:
+            raise ValueError(f"k must be an int in 1..dict_size ({self.d_hidden}), got {k!r}")
+        self._check_x(x)
+        a = self.arena()
+        rows, dev = x.shape[0], a.data.device
+        vals = torch.empty(rows, k, dtype=self.dtype, device=dev)
+        idx = torch.empty(rows, k, dtype=torch.int32, device=dev)
+        buf = torch.empty(min(rows, self.ENCODE_ROWS), self._hp, dtype=self.dtype, device=dev)
+        for r0 in range(0, rows, self.ENCODE_ROWS):
+            r1 = min(rows, r0 + self.ENCODE_ROWS)
+            acts = buf[:r1 - r0]
+            ops.encode_fwd(self._flat_x(x[r0:r1]), a.W_enc_hk, a.b_enc, acts, True)
+            ops.topk_rows(acts, self._hp, k, idx_out=idx[r0:r1], val_out=vals[r0:r1])
+        return vals, idx
 
     def decode(self, acts):
         """acts [batch, d_hidden] -> [batch, n_models, d_model] incl. b_dec (crosscoder.py:82-89)."""

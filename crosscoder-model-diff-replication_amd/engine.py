@@ -163,8 +163,13 @@ class Arena:
 class StepWorkspace:
     """All activations / partial-sum slabs of one step, allocated once per (B, shape, dtype)."""
 
-    def __init__(self, B, n, d, h, dtype, device, transposed=None):
+    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None):
+        """topk (a TopK crosscoder's k): forward() masks G1's activations in place to each row's k largest (one
+        cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself."""
         f32 = torch.float32
+        self.topk = topk
+        if topk is not None:
+            transposed = False
         K = n * d
         self.B, self.n, self.d, self.h, self.K, self.dtype = B, n, d, h, K, dtype
         E = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
@@ -205,10 +210,13 @@ class StepWorkspace:
         # this step's decoder-half Adam before G2, and the side stream runs the tail before that Adam)
         # (and the column sums reduced from them, which the side stream's loss tail reads: the NEXT step's
         # reduce runs on torch's stream before that step waits for the side stream)
-        self._slots = [(E(ops.col_part_rows(B), h), E(ops.wave_parts(B, h)), E(h)) for _ in range(2)]
+        # (TopK: the slabs are the mask kernel's -- column sums and selected counts of the masked activations -- and
+        # G1 writes none)
+        self.n_wave = ops.wave_parts(B, h) if topk is None else ops.topk_l0_parts(B, h)
+        col_rows = ops.col_part_rows(B) if topk is None else ops.topk_part_rows(B, h)
+        self._slots = [(E(col_rows, h), E(self.n_wave), E(h)) for _ in range(2)]
         self._slot = 1
         self.acts_colpart, self.l0_part, self.colsum_acts = self._slots[1]
-        self.n_wave = ops.wave_parts(B, h)
         self.n_l1 = ops.reduce_parts(h)
         self.l1_part = E(self.n_l1)  # per 64-latent block: sum_h colsum_acts[h] * tn[h] (= B * l1)
         self.recon = E(B, K)
@@ -340,9 +348,16 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         if ws.tr:
             ops.encode_fwd_t(ws.x, P.W_enc_hk, P.b_enc, ws.acts, ws.acts_t, True, colsum_part=ws.acts_colpart,
                              l0_part=ws.l0_part, mask_bits=ws.mask_bits, tile_ctr=_tile_ctr(ws, 0), pre=x_job)
-        else:
+        elif ws.topk is None:
             ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True, colsum_part=ws.acts_colpart,
                            l0_part=ws.l0_part)
+        else:
+            ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True)
+    if ws.topk is not None:
+        # TopK: the mask in place, before anything else reads the activations; G2, the loss tail, G3 and G4 then see
+        # the masked activations, their column sums and the selected count
+        with _span("topk"):
+            ops.topk_rows(ws.acts, h, ws.topk, out=ws.acts, colsum_part=ws.acts_colpart, l0_part=ws.l0_part)
     if x_job is None:
         ops.reduce_rows(ws.x_colpart, ws.x_colpart.shape[0], K, scale=1.0 / B, out_f32=ws.x_mean)
     acts_job = ops.colsum_job(ws.acts_colpart, ws.acts_colpart.shape[0], h, 1.0, ws.colsum_acts)

@@ -602,3 +602,37 @@ def latent_stats_update(acts, h, k, count, sum_, hist, topk_val, topk_row, row_i
     check(lib().cc_latent_stats_update(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(row_ids), int(row0), int(k),
                                        _ptr(count), _ptr(sum_), _ptr(hist), _ptr(topk_val), _ptr(topk_row),
                                        _stream(acts)))
+
+
+# ---------------------------------------------------------------- per-row top-k (TopK crosscoders)
+def topk_part_rows(B, h):
+    return int(lib().cc_topk_part_rows(B, h))
+
+
+def topk_l0_parts(B, h):
+    return int(lib().cc_topk_l0_parts(B, h))
+
+
+def topk_rows(acts, h, k, out=None, idx_out=None, val_out=None, colsum_part=None, l0_part=None):
+    """Each row of acts [B, ld >= h] (rows contiguous), first h columns, reduced to its k largest positive values
+    (ties: the smaller latent first; cc_topk_rows).  out: the masked activations (may be `acts` itself: in place);
+    idx_out int32 [B, k] / val_out [B, k] (acts' dtype): the selected pairs by ascending latent, padded with
+    (-1, 0); colsum_part fp32 [topk_part_rows(B, h), h] / l0_part fp32 [topk_l0_parts(B, h)]: column-sum partials
+    and selected counts of the masked activations."""
+    if acts.dim() != 2 or acts.stride(1) != 1:
+        raise ValueError("acts must be [rows, width] with contiguous rows")
+    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    dev = acts.device
+    if out is not None and (out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride()
+                            or out.device != dev):
+        raise ValueError("out must have acts' dtype, shape, strides and device")
+    if (idx_out is None) != (val_out is None):
+        raise ValueError("idx_out and val_out go together")
+    for name, t, dt, shape in (("idx_out", idx_out, torch.int32, (B, k)), ("val_out", val_out, acts.dtype, (B, k)),
+                               ("colsum_part", colsum_part, torch.float32, (topk_part_rows(B, h), h)),
+                               ("l0_part", l0_part, torch.float32, (topk_l0_parts(B, h),))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    check(lib().cc_topk_rows(_ptr(acts), ld, B, h, dtype_code(acts.dtype), int(k), _ptr(out), _ptr(idx_out),
+                             _ptr(val_out), _ptr(colsum_part), _ptr(l0_part), _stream(acts)))
+    return out

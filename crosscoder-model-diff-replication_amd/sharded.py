@@ -280,6 +280,9 @@ class ShardedTrainer:
     cfg["dict_size"] latents; this rank trains its slice)."""
 
     def __init__(self, cfg, buffer, group=None, crosscoder=None, recon_chunks=None, logger=None, comm="all_reduce"):
+        if cfg.get("activation", "relu") == "topk" or getattr(crosscoder, "activation", "relu") == "topk":
+            raise ValueError("ShardedTrainer does not serve activation='topk': a row's top-k across latent shards "
+                             "needs a collective of its own; train TopK crosscoders with Trainer")
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)

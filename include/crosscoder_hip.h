@@ -488,6 +488,27 @@ int cc_latent_stats_update(const void* acts, int64_t ld, int64_t B, int64_t h, i
                            int64_t row0, int k, int64_t* count, float* sum, int64_t* hist, float* topk_val,
                            int64_t* topk_row, void* stream);
 
+/* Per-row top-k of the activations (TopK crosscoders), one pass over acts [B][ld], first h columns
+ * (1 <= k <= h <= 2^17, h % 8 == 0, ld % 8 == 0, ld >= h; acts 16-byte aligned).
+ * An element is eligible iff it is > 0: sign clear, not zero, not NaN; +inf and subnormals are eligible, so the
+ * output of cc_encode_fwd with apply_relu = 0 is legal input and zero padding latents are never selected.
+ * Order: larger value first, among equal values the smaller latent index first (a strict total order); the
+ * selected set of a row is its first min(k, #eligible) elements under that order.
+ * Outputs, each optional (NULL to skip; idx_out and val_out go together):
+ *   acts_out [B][ld]  selected elements keep their exact bits, the other of the h columns become +0; columns
+ *                     >= h are not touched.  acts_out may be acts (in place).
+ *   idx_out [B][k] (int32), val_out [B][k] (dtype): the selected pairs in ascending latent index, padded with
+ *                     (-1, 0) where fewer than k are eligible.
+ *   colsum_part [cc_topk_part_rows(B, h)][h] (fp32, 16-byte aligned): column-sum partials of the masked
+ *                     activations; cc_reduce_rows over them gives sum_b acts.
+ *   l0_part [cc_topk_l0_parts(B, h)] (fp32): selected counts per workgroup (exact integers below 2^24).
+ * No float atomics: two calls on the same input give the same bits in every output.
+ * CC_ERR_SHAPE: k < 1, k > h, h or ld not a multiple of 8, ld < h, B < 1;  CC_ERR_TOO_LARGE: h > 2^17. */
+int64_t cc_topk_part_rows(int64_t B, int64_t h);
+int64_t cc_topk_l0_parts(int64_t B, int64_t h);
+int cc_topk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k, void* acts_out,
+                 int32_t* idx_out, void* val_out, float* colsum_part, float* l0_part, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
