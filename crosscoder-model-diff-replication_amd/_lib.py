@@ -13,8 +13,12 @@ LIB_PATH = os.path.join(_HERE, "libcrosscoder_hip.so")
 # test-only build of the same kernels that also exports the launch-form setters (csrc/Makefile)
 DEBUG_LIB_PATH = os.path.join(_HERE, "libcrosscoder_hip_dbg.so")
 DEFAULT_PP_MASK = 7  # the ping-pong layouts both libraries default to (csrc/gemm.hip: g_pp_mask)
-DEBUG_SETTERS = ("cc_debug_set_pp_mask", "cc_debug_set_pp_fast", "cc_debug_set_dec_one_launch",
-                 "cc_debug_set_wave_sync", "cc_debug_set_epi_store", "cc_debug_set_q4")
+_INT_SETTERS = ("cc_debug_set_pp_mask", "cc_debug_set_pp_fast", "cc_debug_set_dec_one_launch",
+                "cc_debug_set_wave_sync", "cc_debug_set_epi_store", "cc_debug_set_q4", "cc_debug_set_adam_ref")
+# what the debug build exports beyond the header and its probes: the setters, and the exhaustive check of the
+# bf16 Adam's fast primitives against their references (csrc/step_kernels.hip: cc_debug_adam_prims)
+# (named for the setters; test_cpu_host.py checks the debug build's exports against this tuple)
+DEBUG_SETTERS = _INT_SETTERS + ("cc_debug_adam_prims", "cc_debug_adam_redone")
 
 CC_BF16 = 1
 CC_F32 = 2
@@ -158,10 +162,16 @@ def load_debug():
     global _debug
     if _debug is None:
         lib = _open(DEBUG_LIB_PATH)
-        for name in DEBUG_SETTERS:
+        for name in _INT_SETTERS:
             fn = getattr(lib, name)
             fn.restype = None
             fn.argtypes = [ctypes.c_int]
+        # (kind, beta2, step_lo, step_hi, host_out[4], stream)
+        lib.cc_debug_adam_prims.restype = _i
+        lib.cc_debug_adam_prims.argtypes = [_i, _d, _i64, _i64, ctypes.POINTER(ctypes.c_uint64), _p]
+        # (reset) -> 8-element chunks the bf16 Adam launches redid with the reference arithmetic since the last reset
+        lib.cc_debug_adam_redone.restype = _i64
+        lib.cc_debug_adam_redone.argtypes = [_i]
         lib.cc_debug_spin.restype = _i
         lib.cc_debug_spin.argtypes = [_i64, _i64, _i64, _p]
         lib.cc_debug_set_stamps.restype = None
@@ -192,6 +202,7 @@ def debug_library():
         dbg.cc_debug_set_wave_sync(0)
         dbg.cc_debug_set_epi_store(1)
         dbg.cc_debug_set_q4(dbg.q4_default)
+        dbg.cc_debug_set_adam_ref(0)
         _lib = prev
 
 

@@ -5,6 +5,9 @@
 // partial slab (bit-reproducible, no float atomics).
 #include "cc_common.h"
 
+#include <cfloat>
+#include <cmath>
+
 namespace cc {
 
 #include "grad_tail.h"
@@ -363,7 +366,14 @@ struct AdamArgs {
   float w1;         // 1 - beta1 (lerp weight)
   float beta2, omb2, eps;
   float bc2s;       // sqrt(1 - beta2^t)
+  float rb;         // float(1 / (double)bc2s): the bf16 kernels divide by bc2s with it (adam_udiv)
   float neg_step;   // -lr / (1 - beta1^t)
+  // bf16 only: the scalars are inside the fast arithmetic's domain (adam_args); 0 sends every chunk to adam_elem
+  // (the test library's cc_debug_set_adam_ref does that on purpose)
+  int fast;
+#ifdef CC_DEBUG_HOOKS
+  unsigned long long* redo_ctr;  // test library: counts the 8-element chunks redone with adam_elem
+#endif
   // clip coefficient formed in the kernel (instead of read from coef): clip_grad_norm_ over the clip_np
   // per-parameter squared sums clip_sums (e.g. all-reduced over the latent shards); block 0 writes clip_out
   // [coef, total, norms...] like cc_clip_finalize
@@ -444,6 +454,244 @@ CC_DEV void adam_elem(const AdamArgs& a, float coef, float& p, float g, float& m
   v = vj;
 }
 
+// ---------------------------------------------------------------------------------------
+// The bf16 element update with half of adam_elem's vector instructions and the same bits.  Beside G1 the
+// side-stream Adam is bound by vector-instruction issue, not by HBM; adam_elem<CC_BF16>
+// spends most of its instructions on two IEEE divisions and a correctly rounded sqrtf whose results are rounded
+// to bf16 or formed from bf16 operands:
+//   sqrt      vj is a bf16 value: its exact root is never within 2^-19 (relative) of a bf16 rounding boundary,
+//             so the 1-ulp v_sqrt_f32 rounds to the same bf16 as sqrtf
+//   / bc2s    the divisor is uniform: q = den * rb, corrected once with the exact residual (adam_udiv)
+//   mj / den  both bf16 values: fp64 reciprocal, two corrections with the exact residual, one rounding to
+//             fp32 (adam_quot): no operand scaling, exact for any normal operands
+// Each primitive is exact on a domain (zero or normal operands of the right sign); every
+// lane checks its operands, and a wave in which any lane is outside redoes the chunk with adam_elem (one ballot
+// per chunk, the cold block out of line), so the bits are adam_elem's for every input.  The roundings convert two
+// elements per v_cvt_pk_bf16_f32.  The statements are asm so that the kernels keep one instruction per
+// operation: hipcc otherwise pairs adjacent f32 operations into v_pk_*_f32, which beside MFMAs costs more than
+// the two plain instructions.
+constexpr int FPC_NEG_NORMAL = 0x008, FPC_NEG_ZERO = 0x020, FPC_POS_ZERO = 0x040, FPC_POS_NORMAL = 0x100;
+template <int MASK> CC_DEV bool fp_class(float x) { return __builtin_amdgcn_classf(x, MASK); }
+CC_DEV float bf_lo(uint32_t u) { return __uint_as_float(u << 16); }
+CC_DEV float bf_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+// x rounded to bf16, as a float: the conversion's high half with a zero low half
+CC_DEV float round1(float x) {
+  float r;
+  asm("v_cvt_pk_bf16_f32 %0, 0, %1" : "=v"(r) : "v"(x));
+  return r;
+}
+// (x, y) rounded to bf16, as floats; returns the packed pair
+CC_DEV uint32_t round2(float& x, float& y) {
+  uint32_t u;
+  asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(u) : "v"(x), "v"(y));
+  x = bf_lo(u);
+  y = bf_hi(u);
+  return u;
+}
+// One instruction each, opaque to the SLP vectoriser.  `s` operands are wave-uniform (an SGPR: the update's
+// scalars cost no vector registers; one per instruction)
+CC_DEV float op_mul(float a, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+CC_DEV float op_mul_s(float s, float b) { float r; asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "s"(s), "v"(b)); return r; }
+CC_DEV float op_add(float a, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+CC_DEV float op_add_s(float s, float b) { float r; asm("v_add_f32 %0, %1, %2" : "=v"(r) : "s"(s), "v"(b)); return r; }
+CC_DEV float op_sub(float a, float b) { float r; asm("v_sub_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b)); return r; }
+CC_DEV float op_fma(float a, float b, float c) {  // a * b + c
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+CC_DEV float op_fma_s(float a, float s, float c) {  // a * s + c
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(s), "v"(c));
+  return r;
+}
+CC_DEV float op_fma_nc(float a, float b, float c) {  // a * b - c
+  float r;
+  asm("v_fma_f32 %0, %1, %2, -%3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+CC_DEV float op_fma_na(float a, float b, float c) {  // -a * b + c
+  float r;
+  asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+CC_DEV float op_fma_na_s(float a, float s, float c) {  // -a * s + c
+  float r;
+  asm("v_fma_f32 %0, -%1, %2, %3" : "=v"(r) : "v"(a), "s"(s), "v"(c));
+  return r;
+}
+CC_DEV float uniform(float x) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, x)));
+}
+// the update's wave-uniform scalars (AdamArgs' and the clip coefficient), in SGPRs
+struct AdamU {
+  float coef, w1, omw, beta2, omb2, bc2s, rb, eps, neg_step;
+};
+CC_DEV AdamU adam_uniforms(const AdamArgs& a, float coef) {
+  return {uniform(coef),   uniform(a.w1), uniform(1.f - a.w1), uniform(a.beta2),   uniform(a.omb2),
+          uniform(a.bc2s), uniform(a.rb), uniform(a.eps),      uniform(a.neg_step)};
+}
+// den / bc2s for den = +0 or a positive normal bf16 value >= 2^-67, rb = float(1 / (double)bc2s), bc2s in
+// [2^-20, 1]: the residual is exact, so the corrected quotient is the correctly rounded one (Markstein)
+CC_DEV float adam_udiv(float den, float bc2s, float rb) {
+  const float q = op_mul_s(rb, den);
+  const float r = op_fma_na_s(q, bc2s, den);
+  return op_fma_s(r, rb, q);
+}
+// A VALU instruction that reads a transcendental's result needs one instruction between the two, and the
+// compiler's hazard pass does not look into asm statements.  So the square roots and their first readers sit in
+// one asm statement that handles two elements: both transcendentals, then both readers (adam_sqrt2).
+//
+// mj / den for bf16 values, two at a time; ok = mj is a zero or normal and den a positive normal.  The quotient
+// is formed in fp64 and rounded once to fp32, so it is the correctly rounded one over that whole domain, overflow
+// and denormal results included (fp32 arithmetic would need the operand scaling of the IEEE sequence there):
+// v_rcp_f64 (about 2^-23 relative) and two corrections with the exact residual leave an error below 2^-60, so a
+// quotient that fp64 holds exactly -- every fp32 rounding tie among them -- comes out exact, and every other
+// quotient of two 8-bit significands is at least 2^-33 away from a rounding boundary.  The residual is formed
+// negated (q * den - mj, then q - r * y), which keeps the sign of a zero mj as the division does.  (Plain C++:
+// the compiler places the wait state after the transcendental itself, and has no packed fp64 to pair into.)
+CC_DEV float adam_quot(float mj, float den) {
+#pragma clang fp contract(off)
+  const double d = den, m = mj;
+  const double y = __builtin_amdgcn_rcp(d);
+  double q = m * y;
+  q = __builtin_fma(-__builtin_fma(q, d, -m), y, q);
+  q = __builtin_fma(-__builtin_fma(q, d, -m), y, q);
+  return (float)q;
+}
+CC_DEV bool adam_quot_ok(float mj, float den) {
+  return fp_class<FPC_POS_NORMAL>(den) &&
+         fp_class<FPC_NEG_NORMAL | FPC_NEG_ZERO | FPC_POS_ZERO | FPC_POS_NORMAL>(mj);
+}
+CC_DEV void adam_quot2(float m0, float m1, float d0, float d1, float& q0, float& q1, bool& ok0, bool& ok1) {
+  q0 = adam_quot(m0, d0);
+  q1 = adam_quot(m1, d1);
+  ok0 = adam_quot_ok(m0, d0);
+  ok1 = adam_quot_ok(m1, d1);
+}
+// R(sqrt vj) for vj = +0 or a positive normal bf16 value (ok = that), two at a time
+CC_DEV void adam_sqrt2(float v0, float v1, float& s0, float& s1, bool& ok0, bool& ok1) {
+  float t0, t1;
+  asm("v_sqrt_f32 %0, %4\n\tv_sqrt_f32 %1, %5\n\tv_cvt_pk_bf16_f32 %2, 0, %0\n\tv_cvt_pk_bf16_f32 %3, 0, %1"
+      : "=&v"(t0), "=&v"(t1), "=&v"(s0), "=&v"(s1)
+      : "v"(v0), "v"(v1));
+  ok0 = fp_class<FPC_POS_ZERO | FPC_POS_NORMAL>(v0);
+  ok1 = fp_class<FPC_POS_ZERO | FPC_POS_NORMAL>(v1);
+}
+// Two elements, one dword of each packed operand, with adam_elem's operations and rounding points; adds the
+// updated parameters' squares to q in element order.  LO: the lerp weight is below 0.5 (uniform, chosen by the
+// caller).  The roundings whose result is stored convert both elements in one instruction; the others convert
+// one element each straight into float form, which is cheaper than a pair plus two re-expansions.  Returns
+// whether both elements stayed inside the primitives' domains.
+template <bool LO>
+CC_DEV bool adam_pair(const AdamU& u, uint32_t& up, uint32_t ug, uint32_t& um, uint32_t& uv, float& q) {
+  const float g0 = round1(op_mul_s(u.coef, bf_lo(ug))), g1 = round1(op_mul_s(u.coef, bf_hi(ug)));
+  float m0 = bf_lo(um), m1 = bf_hi(um);
+  const float d0 = op_sub(g0, m0), d1 = op_sub(g1, m1);
+  m0 = LO ? op_fma_s(d0, u.w1, m0) : op_fma_na_s(d0, u.omw, g0);
+  m1 = LO ? op_fma_s(d1, u.w1, m1) : op_fma_na_s(d1, u.omw, g1);
+  um = round2(m0, m1);
+  float v0 = round1(op_mul_s(u.beta2, bf_lo(uv))), v1 = round1(op_mul_s(u.beta2, bf_hi(uv)));
+  v0 = op_add(v0, op_mul(op_mul_s(u.omb2, g0), g0));
+  v1 = op_add(v1, op_mul(op_mul_s(u.omb2, g1), g1));
+  uv = round2(v0, v1);
+  // den = R(R(R(sqrt vj) / bc2s) + eps)
+  float s0, s1, x0, x1;
+  bool in0, in1, in2, in3;
+  adam_sqrt2(v0, v1, s0, s1, in0, in1);
+  s0 = round1(op_add_s(u.eps, round1(adam_udiv(s0, u.bc2s, u.rb))));
+  s1 = round1(op_add_s(u.eps, round1(adam_udiv(s1, u.bc2s, u.rb))));
+  adam_quot2(m0, m1, s0, s1, x0, x1, in2, in3);
+  float p0 = op_add(bf_lo(up), op_mul_s(u.neg_step, x0));
+  float p1 = op_add(bf_hi(up), op_mul_s(u.neg_step, x1));
+  up = round2(p0, p1);
+  q = op_fma(p0, p0, q);
+  q = op_fma(p1, p1, q);
+  return in0 && in1 && in2 && in3;
+}
+// One whole 8-element chunk at element i, packed, in place; returns the updated parameters' squares summed in
+// element order (the decoder norms' per-lane term).  The cold block loads its operands again (nothing has been
+// stored yet), so the originals need no registers while the fast arithmetic runs.
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+template <bool NT> CC_DEV bf16x8 ld_bf16x8(const void* base, int64_t i) {
+  const bf16x8* q = (const bf16x8*)((const bf16_t*)base + i);
+  if constexpr (NT) return __builtin_nontemporal_load(q);
+  else return *q;
+}
+template <bool NT> CC_DEV void st_bf16x8(void* base, int64_t i, bf16x8 x) {
+  bf16x8* q = (bf16x8*)((bf16_t*)base + i);
+  if constexpr (NT) __builtin_nontemporal_store(x, q);
+  else *q = x;
+}
+template <bool LO>
+CC_DEV float adam_chunk_bf16(const AdamArgs& a, float coef, int64_t i, bf16x8& p, const bf16x8& g, bf16x8& m,
+                             bf16x8& v) {
+  u32x4 P = __builtin_bit_cast(u32x4, p), M = __builtin_bit_cast(u32x4, m), V = __builtin_bit_cast(u32x4, v);
+  const u32x4 G = __builtin_bit_cast(u32x4, g);
+  const AdamU u = adam_uniforms(a, coef);  // (loop-invariant in the callers)
+  float q = 0.f;
+  bool ok = a.fast != 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    uint32_t pk = P[k], mk = M[k], vk = V[k];
+    const bool in = adam_pair<LO>(u, pk, G[k], mk, vk, q);
+    ok = ok && in;
+    P[k] = pk; M[k] = mk; V[k] = vk;
+  }
+  p = __builtin_bit_cast(bf16x8, P);
+  m = __builtin_bit_cast(bf16x8, M);
+  v = __builtin_bit_cast(bf16x8, V);
+  if (__builtin_expect(__builtin_amdgcn_ballot_w64(!ok) != 0, 0)) {
+    const bf16x8 p0 = ld_bf16x8<true>(a.p, i), g0 = ld_bf16x8<true>(a.g, i), m0 = ld_bf16x8<true>(a.m, i),
+                 v0 = ld_bf16x8<true>(a.v, i);
+#ifdef CC_DEBUG_HOOKS
+    if (a.redo_ctr) atomicAdd(a.redo_ctr, 1ull);
+#endif
+    q = 0.f;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      float pj = bf2f((bf16_t)p0[j]), mj = bf2f((bf16_t)m0[j]), vj = bf2f((bf16_t)v0[j]);
+      adam_elem<CC_BF16>(a, coef, pj, bf2f((bf16_t)g0[j]), mj, vj);
+      p[j] = (short)f2bf(pj);
+      m[j] = (short)f2bf(mj);
+      v[j] = (short)f2bf(vj);
+      q = __fmaf_rn(pj, pj, q);
+    }
+  }
+  return q;
+}
+// (row, column) of a thread's chunk in the decoder-norm matrix [norm_rows][norm_ld], carried through the
+// grid-stride loop: one division per thread instead of a 64-bit one per chunk
+struct NormPos {
+  int row, col, drow, dcol;
+};
+CC_DEV NormPos norm_pos(const AdamArgs& a, int64_t i, int64_t stride) {
+  NormPos n = {0, 0, 0, 0};
+  if (a.norm_part) {
+    n.row = (int)(i / a.norm_ld);
+    n.col = (int)(i - (int64_t)n.row * a.norm_ld);
+    n.drow = (int)(stride / a.norm_ld);
+    n.dcol = (int)(stride - (int64_t)n.drow * a.norm_ld);
+  }
+  return n;
+}
+CC_DEV void norm_pos_next(NormPos& n, int ld) {
+  n.row += n.drow;
+  n.col += n.dcol;
+  if (n.col >= ld) {
+    n.col -= ld;
+    ++n.row;
+  }
+}
+// the chunk's partial of its (row, 64-column block): the 8 lanes of an aligned group hold one block (i % 64 ==
+// 8 * (lane & 7): the grid stride is a multiple of 64, K % 64 == 0), all of them inside the matrix together
+CC_DEV void norm_part_store(const AdamArgs& a, const NormPos& n, float q) {
+  if (a.norm_part && n.row < a.norm_rows) {
+    q = block8_sum(q);
+    if ((threadIdx.x & 7) == 0) a.norm_part[(int64_t)n.row * (a.norm_ld >> 6) + (n.col >> 6)] = q;
+  }
+}
+
 // cache policy of the bulk (encoder-half / whole-arena) Adam: g / m / v non-temporal, p temporal (the
 // updated weights stay in the Infinity Cache for the next GEMM that reads them; measured faster than all
 // temporal or all non-temporal)
@@ -452,15 +700,38 @@ constexpr int ADAM_U = 1;
 // Bulk of the arena: U 8-element chunks per thread, all 4*U loads issued before any math, one
 // pass over the grid (no grid-stride loop).  U = 1 measured fastest (390 us for the 151 M-element
 // config-2 arena = 5.4 TB/s; U = 2: 398 us; the grid-stride loop: 431 us).
-template <int DT, int U>
+// (LO: the lerp form, chosen by the launcher like adam_pipe_kernel's; bf16 only)
+template <int DT, int U, bool LO>
 __global__ __launch_bounds__(256) void adam_bulk_kernel(const AdamArgs a, int64_t nchunks) {
   const int64_t c0 = (int64_t)blockIdx.x * 256 * U + threadIdx.x;
+  constexpr bool PN = false, SN = true;
+  if constexpr (DT == CC_BF16) {  // packed, the fast arithmetic (adam_chunk_bf16)
+    bf16x8 p[U], g[U], m[U], v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t c = c0 + u * 256;
+      if (c < nchunks) {
+        p[u] = ld_bf16x8<PN>(a.p, c * 8); g[u] = ld_bf16x8<SN>(a.g, c * 8); m[u] = ld_bf16x8<SN>(a.m, c * 8);
+        v[u] = ld_bf16x8<SN>(a.v, c * 8);
+      }
+    }
+    const float coef = adam_coef_block(a);  // (placed as below)
+    if (coef < 0.f) return;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t c = c0 + u * 256;
+      if (c < nchunks) {
+        adam_chunk_bf16<LO>(a, coef, c * 8, p[u], g[u], m[u], v[u]);
+        st_bf16x8<PN>(a.p, c * 8, p[u]); st_bf16x8<SN>(a.m, c * 8, m[u]); st_bf16x8<SN>(a.v, c * 8, v[u]);
+      }
+    }
+    return;
+  }
   float p[U][8], g[U][8], m[U][8], v[U][8];
 #pragma unroll
   for (int u = 0; u < U; ++u) {
     const int64_t c = c0 + u * 256;
     if (c < nchunks) {
-      constexpr bool PN = false, SN = true;
       ld8<DT, PN>(a.p, c * 8, p[u]); ld8<DT, SN>(a.g, c * 8, g[u]); ld8<DT, SN>(a.m, c * 8, m[u]);
       ld8<DT, SN>(a.v, c * 8, v[u]);
     }
@@ -475,13 +746,12 @@ __global__ __launch_bounds__(256) void adam_bulk_kernel(const AdamArgs a, int64_
     if (c < nchunks) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) adam_elem<DT>(a, coef, p[u][j], g[u][j], m[u][j], v[u][j]);
-      constexpr bool PN = false, SN = true;
       st8<DT, PN>(a.p, c * 8, p[u]); st8<DT, SN>(a.m, c * 8, m[u]); st8<DT, SN>(a.v, c * 8, v[u]);
     }
   }
 }
 
-template <int DT>
+template <int DT, bool LO>
 __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
   using E = Elem<DT>;
   // (per thread, once before the grid-stride loop: no LDS, so its workgroups still fit beside a GEMM
@@ -491,9 +761,20 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
   // (CC_CLIP_ABORTED: the step's update is not applied -- p / m / v and the norm partials stay as they are --
   // but the done count still arrives)
   const int64_t numel = coef < 0.f ? 0 : a.numel;
-  for (int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8; i < numel; i += stride) {
-    float p[8], g[8], m[8], v[8];
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  NormPos np = norm_pos(a, i0, stride);
+  for (int64_t i = i0; i < numel; i += stride, norm_pos_next(np, a.norm_ld)) {
     const bool full = i + 8 <= a.numel;
+    if constexpr (DT == CC_BF16) {
+      if (full) {  // packed, the fast arithmetic (adam_chunk_bf16)
+        bf16x8 p = ld_bf16x8<true>(a.p, i), g = ld_bf16x8<true>(a.g, i), m = ld_bf16x8<true>(a.m, i),
+               v = ld_bf16x8<true>(a.v, i);
+        norm_part_store(a, np, adam_chunk_bf16<LO>(a, coef, i, p, g, m, v));
+        st_bf16x8<true>(a.p, i, p); st_bf16x8<true>(a.m, i, m); st_bf16x8<true>(a.v, i, v);
+        continue;
+      }
+    }
+    float p[8], g[8], m[8], v[8];
     if (full) {
       load8_nt<DT>(a.p, i, p); load8_nt<DT>(a.g, i, g); load8_nt<DT>(a.m, i, m); load8_nt<DT>(a.v, i, v);
     } else {
@@ -507,34 +788,13 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamArgs a) {
       }
     }
     // torch's CPU/GPU kernels: lerp is an fma (Lerp.h vectorised path), every other op is a
-    // separately rounded fp32 multiply/add -> no contraction here.
+    // separately rounded fp32 multiply/add -> no contraction (adam_elem).
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-#pragma clang fp contract(off)
-      float gj = E::round(g[j] * coef);
-      float w = a.w1;
-      float mj = w < 0.5f ? __builtin_fmaf(w, gj - m[j], m[j]) : __builtin_fmaf(-(gj - m[j]), 1.f - w, gj);
-      mj = E::round(mj);
-      float vj = E::round(v[j] * a.beta2);
-      vj = E::round(vj + a.omb2 * gj * gj);
-      float den = E::round(sqrtf(vj));
-      den = E::round(den / a.bc2s);
-      den = E::round(den + a.eps);
-      float pj = E::round(p[j] + a.neg_step * (mj / den));
-      p[j] = pj; m[j] = mj; v[j] = vj;
-    }
-    if (a.norm_part && i < (int64_t)a.norm_rows * a.norm_ld) {
-      // the 8 lanes of an aligned group hold one 64-column block of a row (i % 64 == 8 * (lane & 7): the
-      // grid stride is a multiple of 64, K % 64 == 0), all of them inside the matrix together
-      float q = 0.f;
+    for (int j = 0; j < 8; ++j) adam_elem<DT>(a, coef, p[j], g[j], m[j], v[j]);
+    float q = 0.f;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) q = __fmaf_rn(p[j], p[j], q);
-      q = block8_sum(q);
-      if ((threadIdx.x & 7) == 0) {
-        const int row = (int)(i / a.norm_ld);
-        a.norm_part[(int64_t)row * (a.norm_ld >> 6) + ((int)(i - (int64_t)row * a.norm_ld) >> 6)] = q;
-      }
-    }
+    for (int j = 0; j < 8; ++j) q = __fmaf_rn(p[j], p[j], q);
+    norm_part_store(a, np, q);
     if (full) {
       store8_nt<DT>(a.p, i, p);
       store8_nt<DT>(a.m, i, m); store8_nt<DT>(a.v, i, v);
@@ -560,34 +820,24 @@ CC_DEV void adam_pipe_load(const AdamArgs& a, int64_t i, bf16x8& p, bf16x8& g, b
   m = __builtin_nontemporal_load((const bf16x8*)((const bf16_t*)a.m + i));
   v = __builtin_nontemporal_load((const bf16x8*)((const bf16_t*)a.v + i));
 }
-__global__ __launch_bounds__(256) void adam_pipe_kernel(const AdamArgs a) {
+// LO: the lerp weight 1 - beta1 is below 0.5 (chosen by the launcher: adam_chunk_bf16).
+// amdgpu_waves_per_eu(6): at most 80 VGPRs (78 used), the room G1's 2 x 216 leave on a SIMD; without it the
+// scheduler interleaves the four pairs of a chunk and takes 104.
+template <bool LO>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void adam_pipe_kernel(const AdamArgs a) {
   const float coef = adam_coef(a);
   const int64_t stride = (int64_t)gridDim.x * 256 * 8;
   const int64_t numel = coef < 0.f ? 0 : a.numel;  // (CC_CLIP_ABORTED: as adam_kernel)
   int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  NormPos np = norm_pos(a, i, stride);
   bf16x8 p, g, m, v;
   if (i < numel) adam_pipe_load(a, i, p, g, m, v);
-  for (; i < numel; i += stride) {
+  for (; i < numel; i += stride, norm_pos_next(np, a.norm_ld)) {
     const int64_t nx = i + stride;
     bf16x8 p2 = p, g2 = g, m2 = m, v2 = v;
     if (nx < numel) adam_pipe_load(a, nx, p2, g2, m2, v2);
-    float q = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float pj = bf2f((bf16_t)p[j]), mj = bf2f((bf16_t)m[j]), vj = bf2f((bf16_t)v[j]);
-      adam_elem<CC_BF16>(a, coef, pj, bf2f((bf16_t)g[j]), mj, vj);
-      p[j] = (short)f2bf(pj);
-      m[j] = (short)f2bf(mj);
-      v[j] = (short)f2bf(vj);
-      q = __fmaf_rn(pj, pj, q);
-    }
-    if (a.norm_part && i < (int64_t)a.norm_rows * a.norm_ld) {  // (as adam_kernel)
-      q = block8_sum(q);
-      if ((threadIdx.x & 7) == 0) {
-        const int row = (int)(i / a.norm_ld);
-        a.norm_part[(int64_t)row * (a.norm_ld >> 6) + ((int)(i - (int64_t)row * a.norm_ld) >> 6)] = q;
-      }
-    }
+    const float q = adam_chunk_bf16<LO>(a, coef, i, p, g, m, v);
+    norm_part_store(a, np, q);  // (as adam_kernel)
     __builtin_nontemporal_store(p, (bf16x8*)((bf16_t*)a.p + i));
     __builtin_nontemporal_store(m, (bf16x8*)((bf16_t*)a.m + i));
     __builtin_nontemporal_store(v, (bf16x8*)((bf16_t*)a.v + i));
@@ -601,9 +851,11 @@ __global__ __launch_bounds__(256) void adam_pipe_kernel(const AdamArgs a) {
 // and the decoder norms' per-(row, 64-column block) squared sums in dec_norms_kernel's order
 // (8 sequential fma per lane, xor-1/2/4 butterfly) -- one HBM pass instead of Adam + a
 // transpose/norms pass.  Persistent grid over the tiles, rows fast; every element gets
-// adam_elem, so p / m / v are the bits cc_adam_step produces.
-// (64 VGPRs: one half-tile's 4 x 8 elements per thread at a time, so it fits beside a 2-wave-per-SIMD
-// ping-pong GEMM's 208)
+// adam_chunk_bf16, so p / m / v are the bits cc_adam_step produces.
+// (90 VGPRs -- 66 with adam_elem alone, before the fast arithmetic and its cold block shared the kernel: one
+// half-tile's 4 x 8 elements per thread at a time; it still fits the 96 a 2-wave-per-SIMD ping-pong GEMM's 2 x 208
+// leave.  adam_kernel<CC_BF16> is at 89 for the same reason; it runs with the whole chip.)
+template <bool LO>
 __global__ __launch_bounds__(256) void adam_dec_tr_kernel(const AdamArgs a, int h, int K, char* __restrict__ wt,
                                                           float* __restrict__ part) {
   __shared__ __attribute__((aligned(16))) char tile[64 * 128];
@@ -614,24 +866,16 @@ __global__ __launch_bounds__(256) void adam_dec_tr_kernel(const AdamArgs a, int 
   const int g4 = lane >> 4, i = lane & 15, q4 = i >> 2, p4 = i & 3;
   for (int t = blockIdx.x; t < ntiles; t += gridDim.x) {
     const int r0 = (t % nr) * 64, c0 = (t / nr) * 64;
-#pragma unroll
+#pragma unroll 1
     for (int k = 0; k < 2; ++k) {
       const int idx = threadIdx.x + 256 * k, r = idx >> 3, ch = idx & 7;
       float qs = 0.f;
       if (r0 + r < h) {
-        float p[8], g[8], m[8], v[8];
         const int64_t e = (int64_t)(r0 + r) * K + c0 + 8 * ch;
-        load8_nt<CC_BF16>(a.p, e, p); load8_nt<CC_BF16>(a.g, e, g);
-        load8_nt<CC_BF16>(a.m, e, m); load8_nt<CC_BF16>(a.v, e, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) adam_elem<CC_BF16>(a, coef, p[j], g[j], m[j], v[j]);
-        store8_nt<CC_BF16>(a.p, e, p); store8_nt<CC_BF16>(a.m, e, m); store8_nt<CC_BF16>(a.v, e, v);
-        bf16x8 b;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          b[j] = (short)f2bf(p[j]);
-          qs = __fmaf_rn(p[j], p[j], qs);
-        }
+        bf16x8 b = ld_bf16x8<true>(a.p, e), g = ld_bf16x8<true>(a.g, e), m = ld_bf16x8<true>(a.m, e),
+               v = ld_bf16x8<true>(a.v, e);
+        qs = adam_chunk_bf16<LO>(a, coef, e, b, g, m, v);
+        st_bf16x8<true>(a.p, e, b); st_bf16x8<true>(a.m, e, m); st_bf16x8<true>(a.v, e, v);
         *(bf16x8*)(tile + r * 128 + ((ch ^ (r & 7)) << 4)) = b;
       }
       qs = block8_sum(qs);
@@ -659,6 +903,13 @@ static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace cc
 
 using namespace cc;
+
+// the bf16 Adam kernels' lerp form (adam_pair): LO_ = the weight 1 - beta1 is below 0.5
+#define ADAM_LO(args, KERNEL_CALL)                                              \
+  do {                                                                          \
+    if ((args).w1 < 0.5f) { constexpr bool LO_ = true; KERNEL_CALL; }           \
+    else { constexpr bool LO_ = false; KERNEL_CALL; }                           \
+  } while (0)
 
 #define DISPATCH_DT(dtype, KERNEL_CALL)                                   \
   do {                                                                    \
@@ -884,6 +1135,141 @@ int cc_segment_sums(const float* sq, const int64_t* off, int nparams, int zero_m
 
 }  // extern "C"
 
+// The test-only debug build (-DCC_DEBUG_HOOKS, libcrosscoder_hip_dbg.so): every bf16 Adam entry on the reference
+// arithmetic (adam_elem) on request, and the fast primitives against their references over whole domains.
+#ifdef CC_DEBUG_HOOKS
+#include <vector>
+#define CC_DEBUG_API extern "C" __attribute__((visibility("default")))
+static int g_adam_ref = 0;
+CC_DEBUG_API void cc_debug_set_adam_ref(int on) { g_adam_ref = on; }
+// The number of 8-element chunks the bf16 Adam launches redid with adam_elem since the last reset (synchronises
+// the device; -1: a HIP error).  A test that compares the fast arithmetic with the reference reads it to know that
+// the fast path produced the compared bits.
+static unsigned long long* g_redo_ctr = nullptr;
+static unsigned long long* debug_redo_ctr() {
+  if (!g_redo_ctr && (hipMalloc((void**)&g_redo_ctr, 8) != hipSuccess || hipMemset(g_redo_ctr, 0, 8) != hipSuccess))
+    g_redo_ctr = nullptr;
+  return g_redo_ctr;
+}
+CC_DEBUG_API int64_t cc_debug_adam_redone(int reset) {
+  unsigned long long n = 0;
+  unsigned long long* ctr = debug_redo_ctr();
+  if (!ctr || hipDeviceSynchronize() != hipSuccess) return -1;
+  if (hipMemcpy(&n, ctr, 8, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+  if (reset && hipMemset(ctr, 0, 8) != hipSuccess) return -1;
+  return (int64_t)n;
+}
+
+// out: [0] mismatches, [1] operands sent to the reference by the guard, [2] the smallest mismatching operand key
+// (atomic min; ~0: none), [3] kind 1: mismatches before the bf16 rounding; kind 2: guarded pairs whose members
+// are all normal or zero with den > 0 (none: adam_quot's guard is on the operands' classes alone)
+struct PrimArgs {
+  int kind;
+  const float* div;  // kind 1: [gridDim.y][2] = (bc2s, rb)
+  unsigned long long* out;
+};
+CC_DEV bool same_bits(float x, float y) { return __float_as_uint(x) == __float_as_uint(y) || (x != x && y != y); }
+__global__ __launch_bounds__(256) void adam_prims_kernel(const PrimArgs a) {
+  const uint32_t idx = blockIdx.x * 256 + threadIdx.x;
+  unsigned long long bad = 0, guarded = 0, aux = 0, first = ~0ull;
+  if (a.kind == 0) {  // sqrt then the bf16 round: idx = vj's bf16 pattern (the pair's other slot: idx ^ 0x5a5a)
+    const float v0 = bf2f((bf16_t)idx), v1 = bf2f((bf16_t)(idx ^ 0x5a5a));
+    float s0, s1;
+    bool ok0, ok1;
+    adam_sqrt2(v0, v1, s0, s1, ok0, ok1);
+    guarded = !ok0;  // (every pattern is slot 0 of one thread)
+    if ((ok0 && !same_bits(s0, Elem<CC_BF16>::round(sqrtf(v0)))) ||
+        (ok1 && !same_bits(s1, Elem<CC_BF16>::round(sqrtf(v1))))) {
+      bad = 1;
+      first = idx;
+    }
+  } else if (a.kind == 1) {  // den / bc2s then the bf16 round: idx = den's pattern, blockIdx.y = divisor
+    const float den = bf2f((bf16_t)idx);
+    const float bc2s = uniform(a.div[2 * blockIdx.y]), rb = uniform(a.div[2 * blockIdx.y + 1]);
+    // adam_udiv's domain: what R(sqrt(vj)) can be for a vj that passed adam_sqrt2's guard (+0, or 2^-63 .. 2^64),
+    // with the margin its proof allows below
+    const bool ok = den == 0.f ? fp_class<FPC_POS_ZERO>(den) : den >= 0x1p-67f && den <= 0x1p64f;
+    const float fast = adam_udiv(den, bc2s, rb), ref = den / bc2s;
+    guarded = !ok;
+    if (ok && !same_bits(fast, ref)) aux = 1;
+    if (ok && !same_bits(Elem<CC_BF16>::round(fast), Elem<CC_BF16>::round(ref))) {
+      bad = 1;
+      first = ((unsigned long long)blockIdx.y << 16) | idx;
+    }
+  } else {  // mj / den: idx = (den pattern << 12) | (mj pattern >> 4), 16 mj patterns per thread, two at a time
+    const float den = bf2f((bf16_t)(idx >> 12));
+    for (uint32_t j = 0; j < 16; j += 2) {
+      const uint32_t mb = ((idx & 0xfffu) << 4) | j;
+      const float m[2] = {bf2f((bf16_t)mb), bf2f((bf16_t)(mb + 1))};
+      float fast[2];
+      bool ok[2];
+      adam_quot2(m[0], m[1], den, den, fast[0], fast[1], ok[0], ok[1]);
+      for (int t = 0; t < 2; ++t) {
+        const bool cls = fp_class<FPC_POS_NORMAL>(den) &&
+                         fp_class<FPC_NEG_NORMAL | FPC_NEG_ZERO | FPC_POS_ZERO | FPC_POS_NORMAL>(m[t]);
+        const bool in = cls && ok[t];  // (the update's den is never a denormal: adam_args' eps check)
+        guarded += !in;
+        aux += cls && !in;
+        if (in && !same_bits(fast[t], m[t] / den)) {
+          ++bad;
+          const unsigned long long key = ((unsigned long long)(idx >> 12) << 16) | (mb + t);
+          first = key < first ? key : first;
+        }
+      }
+    }
+  }
+  // one atomic per wave and counter
+  for (int o = 32; o > 0; o >>= 1) {
+    bad += __shfl_xor(bad, o, 64);
+    guarded += __shfl_xor(guarded, o, 64);
+    aux += __shfl_xor(aux, o, 64);
+    const unsigned long long f2 = __shfl_xor(first, o, 64);
+    first = f2 < first ? f2 : first;
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (bad) atomicAdd(a.out, bad);
+    if (guarded) atomicAdd(a.out + 1, guarded);
+    if (first != ~0ull) atomicMin(a.out + 2, first);
+    if (aux) atomicAdd(a.out + 3, aux);
+  }
+}
+// kind 0: sqrt over the 2^16 bf16 patterns; 1: the uniform divide over 2^16 patterns x the divisors of steps
+// [step_lo, step_hi] at beta2 (as adam_args forms them); 2: the quotient over 2^16 x 2^16 pairs.  Synchronous;
+// host_out[4] as PrimArgs::out.
+CC_DEBUG_API int cc_debug_adam_prims(int kind, double beta2, int64_t step_lo, int64_t step_hi, uint64_t* host_out,
+                                     void* stream) {
+  if (!host_out) return CC_ERR_NULL;
+  if (kind < 0 || kind > 2) return CC_ERR_SHAPE;
+  if (kind == 1 && (step_lo <= 0 || step_hi < step_lo || step_hi - step_lo >= 65535)) return CC_ERR_SHAPE;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t ndiv = kind == 1 ? step_hi - step_lo + 1 : 0;
+  char* buf = nullptr;
+  hipError_t e = hipMalloc((void**)&buf, 32 + (size_t)ndiv * 8);
+  if (e != hipSuccess) return CC_ERR_HIP_BASE + (int)e;
+  const unsigned long long init[4] = {0, 0, ~0ull, 0};
+  std::vector<float> div((size_t)ndiv * 2);
+  for (int64_t s = 0; s < ndiv; ++s) {
+    div[2 * s] = (float)sqrt(1.0 - pow(beta2, (double)(step_lo + s)));
+    div[2 * s + 1] = (float)(1.0 / (double)div[2 * s]);
+  }
+  e = hipMemcpyAsync(buf, init, 32, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && ndiv) e = hipMemcpyAsync(buf + 32, div.data(), (size_t)ndiv * 8, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    const PrimArgs a = {kind, (const float*)(buf + 32), (unsigned long long*)buf};
+    const dim3 grid(kind == 2 ? 1u << 20 : 256u, kind == 1 ? (unsigned)ndiv : 1u);
+    hipLaunchKernelGGL(adam_prims_kernel, grid, dim3(256), 0, st, a);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(host_out, buf, 32, hipMemcpyDeviceToHost, st);
+  const hipError_t e2 = hipStreamSynchronize(st);
+  (void)hipFree(buf);
+  if (e == hipSuccess) e = e2;
+  return e == hipSuccess ? CC_OK : CC_ERR_HIP_BASE + (int)e;
+}
+#else
+constexpr int g_adam_ref = 0;
+#endif
+
 static AdamArgs adam_args(void* p, const void* g, void* m, void* v, int64_t numel, const float* coef, double lr,
                           double beta1, double beta2, double eps, int64_t step) {
   AdamArgs a = {};
@@ -896,7 +1282,15 @@ static AdamArgs adam_args(void* p, const void* g, void* m, void* v, int64_t nume
   a.eps = eps;
   double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
   a.bc2s = (float)sqrt(bc2);
+  a.rb = (float)(1.0 / (double)a.bc2s);
   a.neg_step = (float)(-((double)lr / bc1));
+  // the domain of adam_udiv's divisor and of the sum den + eps (eps: +0 or a positive normal, so that the sum is
+  // no denormal); anything else runs adam_elem
+  a.fast = a.bc2s >= 0x1p-20f && a.bc2s <= 1.f && (a.eps == 0.f || (a.eps >= FLT_MIN && a.eps <= FLT_MAX)) &&
+           !std::signbit(a.eps) && !g_adam_ref;
+#ifdef CC_DEBUG_HOOKS
+  a.redo_ctr = debug_redo_ctr();
+#endif
   return a;
 }
 static int adam_launch(const AdamArgs& a, int64_t max_blocks, int dtype, hipStream_t st);
@@ -914,8 +1308,8 @@ int cc_adam_dec_transposed(void* p, const void* g, void* m, void* v, int64_t h, 
   const AdamArgs a = adam_args(p, g, m, v, h * K, coef, lr, beta1, beta2, eps, step);
   const int64_t ntiles = ((h + 63) / 64) * (K / 64);
   const int64_t blocks = max_blocks > 0 && max_blocks < ntiles ? max_blocks : ntiles;
-  hipLaunchKernelGGL(adam_dec_tr_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a, (int)h, (int)K,
-                     (char*)W_dec_t, part);
+  ADAM_LO(a, hipLaunchKernelGGL(adam_dec_tr_kernel<LO_>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, a,
+                                (int)h, (int)K, (char*)W_dec_t, part));
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
@@ -985,19 +1379,20 @@ static int adam_launch(const AdamArgs& a, int64_t max_blocks, int dtype, hipStre
   if (max_blocks > 0) {  // capped grid-stride form: leaves most CUs to a concurrent GEMM
     const int64_t blocks = adam_capped_blocks(numel, max_blocks);
     if (dtype == CC_BF16 && numel % 8 == 0) {
-      hipLaunchKernelGGL(adam_pipe_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a);
+      ADAM_LO(a, hipLaunchKernelGGL(adam_pipe_kernel<LO_>, dim3((unsigned)blocks), dim3(256), 0, st, a));
       CC_LAUNCH_CHECK();
       return CC_OK;
     }
-    DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_kernel<DT_>), dim3((unsigned)blocks), dim3(256), 0, st, a));
+    ADAM_LO(a, DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_kernel<DT_, DT_ != CC_BF16 || LO_>), dim3((unsigned)blocks),
+                                                     dim3(256), 0, st, a)));
     CC_LAUNCH_CHECK();
     return CC_OK;
   }
   const int64_t nchunks = numel / 8;
   if (nchunks > 0) {
     const int64_t blocks = (nchunks + 256 * ADAM_U - 1) / (256 * ADAM_U);
-    DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_bulk_kernel<DT_, ADAM_U>), dim3((unsigned)blocks), dim3(256), 0,
-                                          st, a, nchunks));
+    ADAM_LO(a, DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_bulk_kernel<DT_, ADAM_U, DT_ != CC_BF16 || LO_>),
+                                                     dim3((unsigned)blocks), dim3(256), 0, st, a, nchunks)));
     CC_LAUNCH_CHECK();
   }
   if (numel % 8) {  // the last < 8 elements
@@ -1006,7 +1401,8 @@ static int adam_launch(const AdamArgs& a, int64_t max_blocks, int dtype, hipStre
     AdamArgs t = a;
     t.p = (char*)a.p + off; t.g = (const char*)a.g + off; t.m = (char*)a.m + off; t.v = (char*)a.v + off;
     t.numel = numel % 8;
-    DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_kernel<DT_>), dim3(1), dim3(256), 0, st, t));
+    ADAM_LO(t, DISPATCH_DT(dtype, hipLaunchKernelGGL((adam_kernel<DT_, DT_ != CC_BF16 || LO_>), dim3(1), dim3(256), 0,
+                                                     st, t)));
     CC_LAUNCH_CHECK();
   }
   return CC_OK;

@@ -620,8 +620,9 @@ DEC_ADAM_BLOCKS = 256
 # share of W_dec's rows whose Adam update runs on the side stream beside the next step's G1; the rest (and
 # b_dec) runs on the main stream after G1 with the whole chip.  Beside G1 the
 # side launch gets one wave per SIMD (G1 holds the rest of the register file), which streams slowly once
-# G1 has finished.
-DEC_SIDE_ROWS = 0.92
+# G1 has finished.  Since the bf16 update's instruction count was cut by about 40 % the side launch ends well
+# before G1, so deferring rows no longer pays: 1.0 measured fastest of 0.92 / 0.96 / 1.0.
+DEC_SIDE_ROWS = 1.0
 # False: the decoder half's Adam runs on torch's stream right after the encoder half, with the whole chip (no side
 # stream, nothing deferred) -- the alternative DESIGN.md section 3.3 measures against the overlap with G1
 DEC_ADAM_BESIDE_G1 = True
