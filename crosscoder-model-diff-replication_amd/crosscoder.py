@@ -8,6 +8,7 @@ all of them in one launch; `W_enc` keeps the reference's h-major strides (d, 1, 
 import json
 import pprint
 import weakref
+from collections import OrderedDict
 from pathlib import Path
 from typing import NamedTuple, Optional, Union
 
@@ -58,13 +59,16 @@ def write_checkpoint(state_dict, cfg, save_dir=None, version=0):
     return save_dir, version + 1
 
 
-ACTIVATIONS = ("relu", "topk")
+ACTIVATIONS = ("relu", "topk", "batch_topk")
+TOPK_WEIGHTS = ("decoder_norm", "none")
 
 
 def activation_of(cfg):
     """(activation, k) of a cfg (framework extension; the keys travel in the checkpoint's cfg json): "relu", the
     reference's and the default, or "topk" -- each row keeps its cfg["k"] largest positive pre-activations
-    (ties: the smaller latent), the rest are zero -- which needs cfg["k"], an int in 1..dict_size."""
+    (ties: the smaller latent), the rest are zero -- which needs cfg["k"], an int in 1..dict_size; or "batch_topk"
+    -- the batch keeps its rows * cfg["k"] best (row, latent) pairs, so k is the mean number kept per row -- with
+    the optional keys of batch_topk_options."""
     act = cfg.get("activation", "relu")
     if act not in ACTIVATIONS:
         raise ValueError(f"cfg['activation'] must be one of {ACTIVATIONS}, got {act!r}")
@@ -72,8 +76,24 @@ def activation_of(cfg):
         return act, None
     k = cfg.get("k")
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= cfg["dict_size"]:
-        raise ValueError(f"activation 'topk' needs cfg['k'], an int in 1..dict_size ({cfg['dict_size']}), got {k!r}")
+        raise ValueError(f"activation {act!r} needs cfg['k'], an int in 1..dict_size ({cfg['dict_size']}), got {k!r}")
+    if act == "batch_topk":
+        batch_topk_options(cfg)
     return act, k
+
+
+def batch_topk_options(cfg):
+    """(topk_weight, threshold_beta) of a "batch_topk" cfg: cfg["topk_weight"], "decoder_norm" (the default: a
+    pair's score is its activation times the latent's summed per-model decoder norms, the weight of the L1 term) or
+    "none" (the activation itself); cfg["threshold_beta"], a float in [0, 1), default 0.999: the decay of the
+    running mean of the training batches' threshold scores that serves inference (CrossCoder.threshold)."""
+    weight = cfg.get("topk_weight", "decoder_norm")
+    if weight not in TOPK_WEIGHTS:
+        raise ValueError(f"cfg['topk_weight'] must be one of {TOPK_WEIGHTS}, got {weight!r}")
+    beta = cfg.get("threshold_beta", 0.999)
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not 0 <= beta < 1:
+        raise ValueError(f"cfg['threshold_beta'] must be a float in [0, 1), got {beta!r}")
+    return weight, float(beta)
 
 
 class CrossCoder(nn.Module):
@@ -100,6 +120,13 @@ class CrossCoder(nn.Module):
             self._arena.W_dec().copy_(W_dec)
             self._arena.W_enc().copy_(W_dec.permute(1, 2, 0))
         self._bind_params()
+        if self.activation == "batch_topk":
+            self.topk_weight, self.threshold_beta = batch_topk_options(cfg)
+            # the inference threshold on the score: the running mean of the training batches' threshold scores
+            # (Trainer.step); -1: unset.  Saved and loaded with the state dict (BatchTopK crosscoders only)
+            self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32, device=device))
+        self._thr_set = None  # (threshold's version when it was read as set): encode then skips the host read
+        self._sel_w = None  # (key, tensor): the selection weights of the W_dec they were computed from
         self.d_hidden = d_hidden
         self.save_dir = None
         self.save_version = 0
@@ -174,7 +201,10 @@ class CrossCoder(nn.Module):
         ws = self._ws
         if (ws is None or ws.B != B or ws.x.device != a.data.device
                 or (ws.busy is not None and ws.busy() is not None)):
-            ws = engine.StepWorkspace(B, self.n_models, self._dp, self._hp, self.dtype, a.data.device, topk=self.k)
+            ws = engine.StepWorkspace(B, self.n_models, self._dp, self._hp, self.dtype, a.data.device,
+                                      topk=self.k if self.activation == "topk" else None,
+                                      batch_topk=(self.k, self.topk_weight != "none")
+                                      if self.activation == "batch_topk" else None)
             self._ws = ws
         return ws
 
@@ -194,15 +224,81 @@ class CrossCoder(nn.Module):
         return ops.prep_input(x, None, self.dtype)
 
     # ------------------------------------------------------------------ reference API
-    def encode(self, x, apply_relu=True):
-        """x [batch, n_models, d_model] -> acts [batch, d_hidden] (crosscoder.py:69-80)."""
+    def encode(self, x, apply_relu=True, use_threshold=None):
+        """x [batch, n_models, d_model] -> acts [batch, d_hidden] (crosscoder.py:69-80).  use_threshold (BatchTopK
+        crosscoders): None -- keep the pairs whose score reaches `threshold` if it is set (>= 0), else the rows * k
+        best pairs of the rows given; True -- the threshold (ValueError while it is unset); False -- the rows * k
+        best pairs."""
         a = self.arena()
         xf = self._flat_x(x)
         acts = torch.empty(xf.shape[0], self._hp, dtype=self.dtype, device=xf.device)
         ops.encode_fwd(xf, a.W_enc_hk, a.b_enc, acts, apply_relu)
-        if self.k is not None and apply_relu:  # TopK: each row's k largest positive values (the padding latents are 0)
-            ops.topk_rows(acts, self._hp, self.k, out=acts)
+        if apply_relu:
+            self.activate_(acts, use_threshold)
         return acts[:, :self.d_hidden].contiguous() if self._hp != self.d_hidden else acts
+
+    def activate_(self, acts, use_threshold=None):
+        """The crosscoder's sparsifying activation on acts [rows, kernel h] = relu(pre), in place: nothing (ReLU), each
+        row's k largest positive values (TopK; the padding latents are 0), or the BatchTopK selection / threshold
+        mask under selection_weights() (see encode)."""
+        if self.activation == "topk":
+            ops.topk_rows(acts, self._hp, self.k, out=acts)
+        elif self.activation == "batch_topk":
+            if use_threshold is None:
+                use_threshold = self._threshold_is_set()
+            elif use_threshold and not self._threshold_is_set():
+                raise ValueError("encode(use_threshold=True): the threshold is unset (-1); it is learned by Trainer.step "
+                                 "or loaded with a checkpoint")
+            w = self._selection_weights() if self.topk_weight != "none" else None
+            if use_threshold:
+                ops.threshold_mask(acts, self._hp, self.threshold.reshape(1), weight=w, out=acts)
+            else:
+                ops.batch_topk(acts, self._hp, acts.shape[0] * self.k, weight=w, out=acts)
+        return acts
+
+    def _threshold_is_set(self):
+        """threshold >= 0.  Read on the host (a device synchronise) until it is seen set; a set threshold stays set
+        -- Trainer.step only moves it between positive scores -- unless torch writes the buffer (its version counter
+        changes: load_state_dict, fill_, .to()), which reads it again."""
+        t = self.threshold
+        key = (t.data_ptr(), t._version)
+        if self._thr_set != key:
+            if not float(t) >= 0:
+                return False
+            self._thr_set = key
+        return True
+
+    def _selection_weights(self):
+        """fp32 [kernel h]: the summed per-model decoder norms (0 for the padding latents), from cc_dec_norms; kept
+        while W_dec is the same storage, unwritten by torch (version counter) and by Adam (Arena.updates)."""
+        a = self.arena()
+        a.wait_pending()
+        key = (*engine._norms_token(a), a.updates)
+        if self._sel_w is None or self._sel_w[0] != key:
+            self._sel_w = (key, ops.dec_norms(a.W_dec_hk, self._hp, self.n_models, self._dp)[1])
+        return self._sel_w[1]
+
+    def selection_weights(self):
+        """fp32 [dict_size]: the weights a BatchTopK crosscoder's encode multiplies the activations by to score them --
+        sum_m ||W_dec[h, m]|| for topk_weight "decoder_norm", ones for "none".  The training step scores with ws.tn,
+        the L1 term's norms, which the batch-major step (the only one BatchTopK runs) fills with the same kernel,
+        cc_dec_norms: the same bits for the same W_dec."""
+        if self.activation != "batch_topk":
+            raise ValueError("selection_weights() serves activation 'batch_topk'")
+        if self.topk_weight == "none":
+            return torch.ones(self.d_hidden, dtype=torch.float32, device=self._arena.data.device)
+        return self._selection_weights()[:self.d_hidden].clone()
+
+    def batch_topk_info(self):
+        """The last get_losses() / Trainer.step() selection of a BatchTopK crosscoder (synchronises): threshold (the
+        smallest selected score), selected, ties (pairs at the threshold score that were admitted), eligible,
+        row_count (int32 [batch]: every row's selected count)."""
+        ws = self._ws
+        if self.activation != "batch_topk" or ws is None:
+            raise ValueError("batch_topk_info(): no BatchTopK forward has run")
+        info = ws.bt_info.cpu()
+        return {"threshold": info[0:1].view(torch.float32).item(), "selected": int(info[1]), "ties": int(info[2]),
+                "eligible": int(info[3]), "row_count": ws.bt_row_count.clone()}
 
     ENCODE_ROWS = 4096  # rows encode_topk encodes per launch pair (its one activation buffer)
 
@@ -255,6 +351,16 @@ class CrossCoder(nn.Module):
         if getattr(self, "_arena", None) is not None:
             self._arena.wait_pending()
         return super().state_dict(*args, **kwargs)
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        # a BatchTopK crosscoder takes the reference's four tensors as they are (e.g. a ReLU checkpoint to train on):
+        # its threshold then stays what it is
+        if self.activation == "batch_topk" and "threshold" not in state_dict:
+            meta = getattr(state_dict, "_metadata", None)
+            state_dict = OrderedDict(state_dict, threshold=self.threshold.detach().clone())
+            if meta is not None:
+                state_dict._metadata = meta
+        return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------ checkpoints
     def create_save_dir(self):

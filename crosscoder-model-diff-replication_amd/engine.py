@@ -107,6 +107,9 @@ class Arena:
         self.pending_rest = None
         # a stream already ordered after `pending` by a launch that waited for the Adam in its kernel
         self.pending_ordered = None
+        # Adam launches on this arena so far: they write it without bumping torch's version counters, so what is
+        # cached from the params outside the step (CrossCoder's selection weights) is keyed on this as well
+        self.updates = 0
 
     def enc_part(self):
         return self.data[:self.split]
@@ -163,12 +166,17 @@ class Arena:
 class StepWorkspace:
     """All activations / partial-sum slabs of one step, allocated once per (B, shape, dtype)."""
 
-    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None):
+    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None):
         """topk (a TopK crosscoder's k): forward() masks G1's activations in place to each row's k largest (one
-        cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself."""
+        cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself.
+        batch_topk ((k, weighted) of a BatchTopK crosscoder): instead, to the batch's B * k best pairs (cc_batch_topk,
+        scored with the decoder norms ws.tn when weighted), in the same step form."""
         f32 = torch.float32
         self.topk = topk
-        if topk is not None:
+        self.batch_topk, self.bt_weighted = batch_topk if batch_topk is not None else (None, False)
+        if topk is not None and batch_topk is not None:
+            raise ValueError("topk and batch_topk exclude each other")
+        if topk is not None or batch_topk is not None:
             transposed = False
         K = n * d
         self.B, self.n, self.d, self.h, self.K, self.dtype = B, n, d, h, K, dtype
@@ -212,8 +220,16 @@ class StepWorkspace:
         # reduce runs on torch's stream before that step waits for the side stream)
         # (TopK: the slabs are the mask kernel's -- column sums and selected counts of the masked activations -- and
         # G1 writes none)
-        self.n_wave = ops.wave_parts(B, h) if topk is None else ops.topk_l0_parts(B, h)
-        col_rows = ops.col_part_rows(B) if topk is None else ops.topk_part_rows(B, h)
+        if batch_topk is not None:
+            self.n_wave, col_rows = ops.batch_topk_l0_parts(B, h), ops.batch_topk_part_rows(B, h)
+            # the selection's workspace, its info words (threshold score bits, selected, ties admitted, eligible) and
+            # every row's selected count
+            self.bt_ws = E(ops.batch_topk_ws_bytes(B, h, dtype, self.bt_weighted), dt=torch.uint8)
+            self.bt_info = torch.zeros(4, dtype=torch.int32, device=device)
+            self.bt_row_count = torch.zeros(B, dtype=torch.int32, device=device)
+        else:
+            self.n_wave = ops.wave_parts(B, h) if topk is None else ops.topk_l0_parts(B, h)
+            col_rows = ops.col_part_rows(B) if topk is None else ops.topk_part_rows(B, h)
         self._slots = [(E(col_rows, h), E(self.n_wave), E(h)) for _ in range(2)]
         self._slot = 1
         self.acts_colpart, self.l0_part, self.colsum_acts = self._slots[1]
@@ -326,12 +342,13 @@ def decoder_norms(ws, P):
     _decoder_derived(ws, P)
 
 
-def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True):
+def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None):
     """Forward + reconstruction-loss gradient.  P: params Arena.  x_in [B, n, d] any of
     fp32/bf16, factor [n] or None.  Leaves losses in ws.scalars / ws.ev*, g_recon ready
     (loss=False: stops at the fp32 reconstruction, for loss_rows / loss_finalize by slices;
     finalize=False: stops after the loss rows, for loss_finalize_with_g3 / loss_finalize_beside).  Where the fused entry
-    serves the shape, G2 and the loss rows are one pass (decode_loss_t; no fp32 reconstruction)."""
+    serves the shape, G2 and the loss rows are one pass (decode_loss_t; no fp32 reconstruction).
+    bt_threshold ((tensor, beta), BatchTopK, the Trainer's): the running threshold the selection folds its T into."""
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     ws.next_slot()
     with _span("prep"):
@@ -348,7 +365,7 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         if ws.tr:
             ops.encode_fwd_t(ws.x, P.W_enc_hk, P.b_enc, ws.acts, ws.acts_t, True, colsum_part=ws.acts_colpart,
                              l0_part=ws.l0_part, mask_bits=ws.mask_bits, tile_ctr=_tile_ctr(ws, 0), pre=x_job)
-        elif ws.topk is None:
+        elif ws.topk is None and ws.batch_topk is None:
             ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True, colsum_part=ws.acts_colpart,
                            l0_part=ws.l0_part)
         else:
@@ -358,6 +375,21 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         # the masked activations, their column sums and the selected count
         with _span("topk"):
             ops.topk_rows(ws.acts, h, ws.topk, out=ws.acts, colsum_part=ws.acts_colpart, l0_part=ws.l0_part)
+    norms_done = False
+    if ws.batch_topk is not None:
+        # BatchTopK: the same, one selection over the batch.  Weighted, it is scored with the decoder norms ws.tn (the
+        # L1 term's own), which therefore have to be current before the mask: the wait for the decoder-half Adam and
+        # the norms move ahead of it (G1 above still overlaps that Adam).  Unweighted, they stay where TopK has them
+        if ws.bt_weighted:
+            P.wait_pending()
+            decoder_norms(ws, P)
+            flush_norms(ws)
+            norms_done = True
+        thr, beta = bt_threshold if bt_threshold is not None else (None, 0.0)
+        with _span("batch_topk"):
+            ops.batch_topk(ws.acts, h, B * ws.batch_topk, weight=ws.tn if ws.bt_weighted else None, out=ws.acts,
+                           colsum_part=ws.acts_colpart, l0_part=ws.l0_part, row_count=ws.bt_row_count,
+                           info=ws.bt_info, ws=ws.bt_ws, threshold=thr, beta=beta)
     if x_job is None:
         ops.reduce_rows(ws.x_colpart, ws.x_colpart.shape[0], K, scale=1.0 / B, out_f32=ws.x_mean)
     acts_job = ops.colsum_job(ws.acts_colpart, ws.acts_colpart.shape[0], h, 1.0, ws.colsum_acts)
@@ -365,11 +397,12 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
     # the latent-sharded step's G2 (decode_partial_jobs: W_dec read as stored, bf16) waits in its kernel too
     partial_g2 = bool(not loss and ws.tr and ws.W_dec_t is None)
     # (only while the decoder norms are the Adam's own: otherwise decoder_norms below reads W_dec on this stream)
-    wait = P.wait_pending(kernel_wait=(fused_g2 or partial_g2) and G2_WAITS_IN_KERNEL
-                          and ws.norms_token == _norms_token(P))
+    wait = None if norms_done else P.wait_pending(kernel_wait=(fused_g2 or partial_g2) and G2_WAITS_IN_KERNEL
+                                                  and ws.norms_token == _norms_token(P))
     if wait is not None:
         wait = (*wait, _wait_err(ws))
-    decoder_norms(ws, P)  # (+ W_dec^T), unless launched already after the last Adam
+    if not norms_done:
+        decoder_norms(ws, P)  # (+ W_dec^T), unless launched already after the last Adam
     if fused_g2:
         # (carries a pending norm finaliser and, fused, the activation column sums; waits in its kernel for the
         # side-stream Adam where `wait`)
@@ -647,6 +680,7 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
     later decoder-half use (forward() waits before G2; CrossCoder's accessors, FusedAdam.state and
     Trainer.synchronize() wait).  Without a side stream: one launch over the whole arena."""
     P.wait_pending()  # (no deferred rows of an earlier step may read this step's coefficient)
+    P.updates += 1
     coef = ws.clip_out[0:1]
     emulate = ws.dtype == torch.bfloat16
 

@@ -105,8 +105,7 @@ class LatentStats:
             r1 = min(rows, r0 + CHUNK_ROWS)
             acts = self._acts[:r1 - r0]
             ops.encode_fwd(cc._flat_x(x[r0:r1]), a.W_enc_hk, a.b_enc, acts, True)
-            if cc.k is not None:  # a TopK crosscoder's activations, as cc.encode gives them
-                ops.topk_rows(acts, cc._hp, cc.k, out=acts)
+            cc.activate_(acts)  # a TopK / BatchTopK crosscoder's activations, as cc.encode gives them for these rows
             self.update_from_acts(acts, row_ids=None if ids is None else ids[r0:r1])
 
     def result(self):

@@ -636,3 +636,81 @@ def topk_rows(acts, h, k, out=None, idx_out=None, val_out=None, colsum_part=None
     check(lib().cc_topk_rows(_ptr(acts), ld, B, h, dtype_code(acts.dtype), int(k), _ptr(out), _ptr(idx_out),
                              _ptr(val_out), _ptr(colsum_part), _ptr(l0_part), _stream(acts)))
     return out
+
+
+# ---------------------------------------------------------------- BatchTopK (one selection over the whole batch)
+def batch_topk_part_rows(B, h):
+    return int(lib().cc_batch_topk_part_rows(B, h))
+
+
+def batch_topk_l0_parts(B, h):
+    return int(lib().cc_batch_topk_l0_parts(B, h))
+
+
+def batch_topk_ws_bytes(B, h, dtype, weighted):
+    return int(lib().cc_batch_topk_ws_bytes(B, h, dtype_code(dtype), int(bool(weighted))))
+
+
+def _batch_topk_args(acts, h, weight, out, colsum_part, l0_part, row_count):
+    if acts.dim() != 2 or acts.stride(1) != 1:
+        raise ValueError("acts must be [rows, width] with contiguous rows")
+    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    dev = acts.device
+    if out is not None and (out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride()
+                            or out.device != dev):
+        raise ValueError("out must have acts' dtype, shape, strides and device")
+    for name, t, dt, shape in (("weight", weight, torch.float32, (h,)),
+                               ("colsum_part", colsum_part, torch.float32, (batch_topk_part_rows(B, h), h)),
+                               ("l0_part", l0_part, torch.float32, (batch_topk_l0_parts(B, h),)),
+                               ("row_count", row_count, torch.int32, (B,))):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    return B, ld
+
+
+def batch_topk(acts, h, n_keep, weight=None, out=None, colsum_part=None, l0_part=None, row_count=None, info=None,
+               ws=None, threshold=None, beta=0.0):
+    """acts [B, ld >= h] (rows contiguous), first h columns, reduced to the n_keep best (row, latent) pairs of the
+    whole batch under score = act * weight[latent] (weight fp32 [h]; None: the activation itself); ties: the
+    smaller flat index row * h + latent first (cc_batch_topk).  out: the masked activations (may be `acts` itself:
+    in place); colsum_part fp32 [batch_topk_part_rows(B, h), h] / l0_part fp32 [batch_topk_l0_parts(B, h)]:
+    column-sum partials and selected counts of the masked activations; row_count int32 [B]: every row's selected
+    count; info uint32-as-int32 [4]: (threshold score bits, selected, ties at the threshold admitted, eligible).
+    ws: a uint8 tensor of at least batch_topk_ws_bytes(...) bytes (allocated when None).  threshold (an fp32 tensor
+    of one element on the device) with beta in [0, 1): the running threshold the last selection launch folds T into
+    (T itself while it is < 0).  Returns out."""
+    B, ld = _batch_topk_args(acts, h, weight, out, colsum_part, l0_part, row_count)
+    if isinstance(n_keep, bool) or not isinstance(n_keep, int) or n_keep < 1:
+        raise ValueError(f"n_keep must be an int >= 1, got {n_keep!r}")
+    if out is None and info is None and row_count is None:
+        raise ValueError("at least one of out, info and row_count is needed")
+    dev = acts.device
+    if info is not None and (info.dtype != torch.int32 or tuple(info.shape) != (4,) or info.device != dev
+                             or not info.is_contiguous()):
+        raise ValueError(f"info must be a contiguous int32 tensor of shape (4,) on {dev}")
+    if threshold is not None and (threshold.dtype != torch.float32 or threshold.numel() != 1
+                                  or threshold.device != dev or not 0 <= beta < 1):
+        raise ValueError(f"threshold must be an fp32 tensor of one element on {dev}, beta a float in [0, 1)")
+    need = batch_topk_ws_bytes(B, h, acts.dtype, weight is not None)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    if ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need:
+        raise ValueError(f"ws must be a contiguous uint8 tensor of at least {need} bytes on {dev}")
+    check(lib().cc_batch_topk(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(weight), int(n_keep), _ptr(out),
+                              _ptr(colsum_part), _ptr(l0_part), _ptr(row_count), _ptr(info), _ptr(threshold), float(beta), _ptr(ws), ws.numel(),
+                              _stream(acts)))
+    return out
+
+
+def threshold_mask(acts, h, theta, weight=None, out=None, colsum_part=None, l0_part=None, row_count=None):
+    """The inference form of batch_topk, one pass: keeps an element iff it is eligible and its score is >= theta
+    (an fp32 tensor of one element on the device: never read on the host; cc_threshold_mask).  The same outputs
+    without info."""
+    B, ld = _batch_topk_args(acts, h, weight, out, colsum_part, l0_part, row_count)
+    if out is None and row_count is None:
+        raise ValueError("at least one of out and row_count is needed")
+    if theta.dtype != torch.float32 or theta.numel() != 1 or theta.device != acts.device:
+        raise ValueError(f"theta must be an fp32 tensor of one element on {acts.device}")
+    check(lib().cc_threshold_mask(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(weight), _ptr(theta), _ptr(out),
+                                  _ptr(colsum_part), _ptr(l0_part), _ptr(row_count), _stream(acts)))
+    return out

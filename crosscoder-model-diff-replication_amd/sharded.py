@@ -283,6 +283,10 @@ class ShardedTrainer:
         if cfg.get("activation", "relu") == "topk" or getattr(crosscoder, "activation", "relu") == "topk":
             raise ValueError("ShardedTrainer does not serve activation='topk': a row's top-k across latent shards "
                              "needs a collective of its own; train TopK crosscoders with Trainer")
+        if cfg.get("activation", "relu") == "batch_topk" or getattr(crosscoder, "activation", "relu") == "batch_topk":
+            raise ValueError("ShardedTrainer does not serve activation='batch_topk': the batch's threshold across "
+                             "latent shards needs a collective of its own (an all-reduce of the histograms); train "
+                             "BatchTopK crosscoders with Trainer")
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)

@@ -127,7 +127,10 @@ class Trainer:
         opt = self.optimizer
         side = self._side_stream()
         # prep, G1, G2 + the loss rows (one pass where decode_loss_t serves the shape)
-        engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False)
+        # (BatchTopK: the selection's last launch folds the step's threshold score T into the crosscoder's inference
+        # threshold -- T at the first step, then beta * threshold + (1 - beta) * T -- on the device, in stream order)
+        engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False,
+                       bt_threshold=(cc.threshold, cc.threshold_beta) if ws.batch_topk is not None else None)
         if self.latent_stats is not None:  # (after G2 and the loss rows, before G3; acts is only read from G1 on: this stream's order suffices)
             self.latent_stats.update_from_acts(ws.acts, row0=self.step_counter * self.cfg["batch_size"])
         # the loss scalars: into mapped host memory from the G3 launch (or, where G3 cannot carry the tail, from a

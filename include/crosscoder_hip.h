@@ -509,6 +509,50 @@ int64_t cc_topk_l0_parts(int64_t B, int64_t h);
 int cc_topk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k, void* acts_out,
                  int32_t* idx_out, void* val_out, float* colsum_part, float* l0_part, void* stream);
 
+/* BatchTopK selection (BatchTopK crosscoders): the n_keep best (row, latent) pairs of the whole batch, over
+ * acts [B][ld], first h columns (h % 8 == 0, ld % 8 == 0, ld >= h, h <= 2^17, B * h <= 2^31, n_keep >= 1; acts,
+ * acts_out, colsum_part and weight 16-byte aligned).
+ * Score: weight == NULL: float(a).  Else the fp32 product float(a) * weight[l] (weight fp32 [h]; one IEEE multiply,
+ * round to nearest).
+ * Eligible: the activation is > 0 and the score is > 0, both on their bits (sign clear, not zero, not NaN; +inf
+ * and subnormals count, the rule of cc_topk_rows).  So a positive activation whose product is 0 (a zero weight, an
+ * underflow) is ineligible, and so is every element under a negative or NaN weight.
+ * Order: larger score first, among equal scores the smaller flat index row * h + latent first (a strict total
+ * order); selected are the first min(n_keep, #eligible) elements under it.
+ * Outputs, each optional (NULL to skip), at least one of acts_out, info, row_count given:
+ *   acts_out [B][ld]  selected elements keep their own activation bits, the other of the h columns become +0;
+ *                     columns >= h are not touched.  acts_out may be acts (in place).
+ *   colsum_part [cc_batch_topk_part_rows(B, h)][h] (fp32): column-sum partials of the masked activations;
+ *                     cc_reduce_rows over them gives sum_b acts.
+ *   l0_part [cc_batch_topk_l0_parts(B, h)] (fp32): selected counts per workgroup (exact integers below 2^24).
+ *   row_count [B] (int32): the selected count of every row.
+ *   info [4] (uint32): the fp32 bits of the threshold score T (the smallest selected score; 0 when nothing is
+ *                     selected), the number selected, the number of elements with score T that were admitted, the
+ *                     number eligible.
+ *   threshold_ema (one fp32 on the device, with 0 <= beta < 1): the running threshold, updated by the launch that
+ *                     writes info when something is selected: T if *threshold_ema < 0 (unset), else
+ *                     beta * *threshold_ema + (1 - beta) * T.
+ * ws: cc_batch_topk_ws_bytes(B, h, dtype, weight != NULL) bytes of device memory (4-byte aligned, any content: the
+ * call zeroes what it needs); ws_bytes: its size.  A radix select in separate launches on `stream` (histogram
+ * passes from the top digit -- two for unweighted bf16, else three -- then one mask pass); integer atomics only,
+ * no float atomics: two calls on the same input give the same bits in every output.
+ * cc_threshold_mask: the inference form, one pass: keeps an element iff it is eligible and score >= *theta (theta:
+ * device pointer to one fp32; NaN keeps nothing); the same outputs without info, at least one of acts_out and
+ * row_count given.
+ * Errors, checked in this order before any launch: CC_ERR_SHAPE (B < 1, h < 8, h or ld not a multiple of 8, ld < h,
+ * n_keep < 1, beta outside [0, 1) with threshold_ema given), CC_ERR_NULL (acts, ws / theta, or no output),
+ * CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h > 2^17, B * h > 2^31), CC_ERR_ALIGN (16 bytes: acts, acts_out, colsum_part,
+ * weight; 4 bytes: the rest); then CC_ERR_SHAPE for a ws_bytes below the size needed. */
+int64_t cc_batch_topk_part_rows(int64_t B, int64_t h);
+int64_t cc_batch_topk_l0_parts(int64_t B, int64_t h);
+int64_t cc_batch_topk_ws_bytes(int64_t B, int64_t h, int dtype, int weighted);
+int cc_batch_topk(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* weight, int64_t n_keep,
+                  void* acts_out, float* colsum_part, float* l0_part, int32_t* row_count, uint32_t* info,
+                  float* threshold_ema, float beta, void* ws, int64_t ws_bytes, void* stream);
+int cc_threshold_mask(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* weight,
+                      const float* theta, void* acts_out, float* colsum_part, float* l0_part, int32_t* row_count,
+                      void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
