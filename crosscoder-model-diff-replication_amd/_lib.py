@@ -129,6 +129,11 @@ SIGNATURES = {
     "cc_adam_dec_norms": (_i, [_p, _p, _p, _p, _i64, _p, _p, _i, _f, _i, _d, _d, _d, _d, _i64, _i64, _p, _i64, _i64, _i,
                                _p, _p]),
     "cc_adam_capped_blocks": (_i64, [_i64, _i64]),
+    "cc_auxk_rows": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _i64, _p, _p, _p]),
+    "cc_dead_update": (_i, [_p, _p, _i64, _i64, _i64, _i64, _p, _p, _p, _p]),
+    "cc_auxk_part_floats": (_i64, [_i64, _i64]),
+    "cc_auxk_loss": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i64, _i64, _i, _p]),
+    "cc_add_rows": (_i, [_p, _p, _i64, _i64, _i64, _i, _p]),
 }
 
 _lib = None

@@ -96,6 +96,31 @@ def batch_topk_options(cfg):
     return weight, float(beta)
 
 
+def auxk_options(cfg, n_models=2):
+    """(auxk_coeff, k_aux, dead_tokens) of a cfg, or None when the AuxK dead-latent loss is off (framework extension;
+    the keys travel in the checkpoint's cfg json).  cfg["auxk_coeff"]: a float >= 0, absent or 0: off.  On, it needs
+    activation "topk" or "batch_topk" and takes cfg["k_aux"], an int in 1..dict_size (default
+    min(dict_size, max(1, n_models * d_in // 2))): how many dead latents per row reconstruct the residual; and
+    cfg["dead_tokens"], an int >= 1 (default 10 000 000): a latent is dead once it has not fired for that many
+    tokens."""
+    coeff = cfg.get("auxk_coeff", 0)
+    if isinstance(coeff, bool) or not isinstance(coeff, (int, float)) or not coeff >= 0 or coeff == float("inf"):
+        raise ValueError(f"cfg['auxk_coeff'] must be a finite float >= 0, got {coeff!r}")
+    if coeff == 0:
+        return None
+    if cfg.get("activation", "relu") == "relu":
+        raise ValueError("cfg['auxk_coeff'] > 0 needs activation 'topk' or 'batch_topk': a ReLU crosscoder's latents "
+                         "get gradient whenever they are positive")
+    h = cfg["dict_size"]
+    k_aux = cfg.get("k_aux", min(h, max(1, n_models * cfg["d_in"] // 2)))
+    if isinstance(k_aux, bool) or not isinstance(k_aux, int) or not 1 <= k_aux <= h:
+        raise ValueError(f"cfg['k_aux'] must be an int in 1..dict_size ({h}), got {k_aux!r}")
+    dead = cfg.get("dead_tokens", 10_000_000)
+    if isinstance(dead, bool) or not isinstance(dead, int) or dead < 1:
+        raise ValueError(f"cfg['dead_tokens'] must be an int >= 1, got {dead!r}")
+    return float(coeff), k_aux, dead
+
+
 class CrossCoder(nn.Module):
     def __init__(self, cfg, n_models: Optional[int] = None, init_W_dec: Optional[torch.Tensor] = None):
         """init_W_dec (framework extension): start from this decoder ([h, n, d], W_enc = its rearranged
@@ -107,6 +132,7 @@ class CrossCoder(nn.Module):
         self.activation, self.k = activation_of(cfg)
         d_in = cfg["d_in"]
         self.n_models = int(n_models if n_models is not None else cfg.get("n_models", 2))
+        self.auxk = auxk_options(cfg, self.n_models)  # (auxk_coeff, k_aux, dead_tokens) or None: Trainer.step's
         self.dtype = DTYPES[cfg["enc_dtype"]]
         if self.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("crosscoder_amd kernels support enc_dtype 'bf16' and 'fp32'")
@@ -204,7 +230,8 @@ class CrossCoder(nn.Module):
             ws = engine.StepWorkspace(B, self.n_models, self._dp, self._hp, self.dtype, a.data.device,
                                       topk=self.k if self.activation == "topk" else None,
                                       batch_topk=(self.k, self.topk_weight != "none")
-                                      if self.activation == "batch_topk" else None)
+                                      if self.activation == "batch_topk" else None,
+                                      auxk=(self.auxk[1],) if self.auxk is not None else None)
             self._ws = ws
         return ws
 

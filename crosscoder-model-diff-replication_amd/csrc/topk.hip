@@ -17,6 +17,12 @@
 // The last pass admits every key above the threshold T and the first `need` keys equal to T in index order
 // (per chunk: a prefix count across lanes, then across waves), which is also each element's output slot.
 // No float atomics: the partial rows and counts are fixed by (B, h) and the input alone.
+//
+// AUX (cc_auxk_rows, the AuxK dead-latent loss): the same selection with a column predicate -- an element's key
+// is 0 unless since_fired[column] >= dead_after.  A lane owns the same columns in every row, so the predicate is
+// loaded once per workgroup (one int64 per owned column) and kept as bits over the row loop: 8 NCH bits in one
+// register, or (NCH = 0, up to 16 chunks) 128 bits in two 64-bit registers.  It writes the dense output and the
+// row counts only.
 #include "cc_common.h"
 
 namespace cc {
@@ -78,11 +84,24 @@ CC_DEV uint32_t tk_wave_incl_scan(uint32_t v, int lane) {
   return v;
 }
 
+// the key under the column predicate: db holds the dead bits of the 8 columns of this lane's chunk
+template <int DT, bool AUX> CC_DEV uint32_t tk_key_if(uint32_t u, uint32_t db, int j) {
+  if constexpr (AUX) return (db >> j) & 1u ? tk_key<DT>(u) : 0u;
+  else return tk_key<DT>(u);
+}
+
 // (acts and acts_out may be the same buffer: no __restrict__ on them)
-template <int DT, int NT, int NCH>
+template <int DT, int NT, int NCH, bool AUX = false>
 __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t ld, int B, int h, int k, void* acts_out,
                                                        int32_t* __restrict__ idx_out, void* __restrict__ val_out,
-                                                       float* __restrict__ colsum_part, float* __restrict__ l0_part) {
+                                                       float* __restrict__ colsum_part, float* __restrict__ l0_part,
+                                                       const int64_t* __restrict__ since_fired = nullptr,
+                                                       int64_t dead_after = 0, int32_t* __restrict__ row_count = nullptr) {
+  if constexpr (AUX) {  // (the dense output and the row counts only)
+    idx_out = nullptr;
+    colsum_part = nullptr;
+    l0_part = nullptr;
+  }
   constexpr int NW = NT / 64, CH = NT * 8, NPASS = DT == CC_BF16 ? 2 : 4;
   constexpr bool REG = NCH > 0;
   constexpr int NR = REG ? NCH : 1;
@@ -92,6 +111,25 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
 
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int nch = REG ? NCH : (h + CH - 1) / CH;
+  // AUX: the dead bits of this lane's columns, chunk c in byte c (REG: of dead_lo's low word)
+  uint64_t dead_lo = 0u, dead_hi = 0u;
+  if constexpr (AUX) {
+    for (int c = 0; c < nch; ++c) {
+      const int col = c * CH + tid * 8;
+      uint64_t b = 0u;
+      if (col < h) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b |= (uint64_t)(since_fired[col + j] >= dead_after ? 1u : 0u) << j;
+      }
+      if (c < 8) dead_lo |= b << (8 * c);
+      else dead_hi |= b << (8 * (c - 8));
+    }
+  }
+  auto dead_bits = [&](int c) -> uint32_t {
+    if constexpr (!AUX) return 0xffu;
+    else if constexpr (REG) return ((uint32_t)dead_lo >> (8 * c)) & 0xffu;
+    else return (uint32_t)((c < 8 ? dead_lo : dead_hi) >> (8 * (c & 7))) & 0xffu;
+  };
   uint32_t* const myhist = hist + (lane & (TK_COPIES - 1));
 
   for (int e = tid; e < TK_BINS * TK_COPIES; e += NT) hist[e] = 0u;
@@ -160,10 +198,11 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
 #pragma unroll 1
     for (int p = 0; p < NPASS; ++p) {
       const int shift = 8 * (NPASS - 1 - p);
-      chunks([&](int, int, const uint32_t (&u)[8]) {
+      chunks([&](int c, int, const uint32_t (&u)[8]) {
+        const uint32_t db = dead_bits(c);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const uint32_t key = tk_key<DT>(u[j]);
+          const uint32_t key = tk_key_if<DT, AUX>(u[j], db, j);
           const bool in = key != 0u && (p == 0 || (key >> ((shift + 8) & 31)) == prefix);
           if (in) atomicAdd(myhist + ((key >> shift) & 255u) * TK_COPIES, 1u);
         }
@@ -216,9 +255,10 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
     uint32_t base_gt = 0u, base_eq = 0u;
     chunks([&](int c, int col, const uint32_t (&u)[8]) {
       uint32_t key[8], mine = 0u;  // mine: (#key > T) << 16 | #key == T, both <= 8
+      const uint32_t db = dead_bits(c);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        key[j] = tk_key<DT>(u[j]);
+        key[j] = tk_key_if<DT, AUX>(u[j], db, j);
         mine += key[j] > T ? 0x10000u : key[j] == T ? 1u : 0u;
       }
       const uint32_t incl = tk_wave_incl_scan(mine, lane);
@@ -265,6 +305,9 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
         else ((uint32_t*)val_out)[(int64_t)row * k + s] = 0u;
       }
     selected_rows += n_sel;
+    if constexpr (AUX) {
+      if (row_count && tid == 0) row_count[row] = (int32_t)n_sel;
+    }
     if constexpr (REG) {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) cur[c] = nxt[c];
@@ -308,6 +351,23 @@ static void tk_launch(const void* acts, int64_t ld, int64_t B, int64_t h, int k,
 #undef TK_GO
 }
 
+template <int DT>
+static void ak_launch(const void* acts, int64_t ld, int64_t B, int64_t h, int k, const int64_t* since_fired,
+                      int64_t dead_after, void* aux_out, int32_t* row_count, hipStream_t st) {
+  const dim3 grid((unsigned)tk_groups(B, h));
+#define AK_GO(NT, NCH)                                                                                                \
+  hipLaunchKernelGGL((topk_rows_kernel<DT, NT, NCH, true>), grid, dim3(NT), 0, st, acts, ld, (int)B, (int)h, k, aux_out, \
+                     (int32_t*)nullptr, (void*)nullptr, (float*)nullptr, (float*)nullptr, since_fired, dead_after,    \
+                     row_count)
+  // (the four forms of tk_launch, by h)
+  if (h <= 2048) AK_GO(256, 1);
+  else if (h <= 8192) AK_GO(1024, 1);
+  else if (DT == CC_BF16 && h <= 16384) {
+    if constexpr (DT == CC_BF16) AK_GO(1024, 2);
+  } else AK_GO(1024, 0);
+#undef AK_GO
+}
+
 }  // namespace cc
 
 using namespace cc;
@@ -329,6 +389,21 @@ int cc_topk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, 
     tk_launch<CC_BF16>(acts, ld, B, h, k, acts_out, idx_out, val_out, colsum_part, l0_part, st);
   else
     tk_launch<CC_F32>(acts, ld, B, h, k, acts_out, idx_out, val_out, colsum_part, l0_part, st);
+  CC_LAUNCH_CHECK();
+  return CC_OK;
+}
+
+int cc_auxk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k_aux, const int64_t* since_fired,
+                 int64_t dead_after, void* aux_out, int32_t* row_count, void* stream) {
+  if (B < 1 || h < 8 || (h & 7) || (ld & 7) || ld < h || k_aux < 1 || k_aux > h) return CC_ERR_SHAPE;
+  if (!acts || !since_fired || !aux_out || aux_out == acts) return CC_ERR_NULL;
+  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
+  if (h > TK_MAX_H || B > (1 << 30)) return CC_ERR_TOO_LARGE;
+  if ((((uintptr_t)acts | (uintptr_t)aux_out) & 15) || ((uintptr_t)since_fired & 7) || ((uintptr_t)row_count & 3))
+    return CC_ERR_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == CC_BF16) ak_launch<CC_BF16>(acts, ld, B, h, k_aux, since_fired, dead_after, aux_out, row_count, st);
+  else ak_launch<CC_F32>(acts, ld, B, h, k_aux, since_fired, dead_after, aux_out, row_count, st);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }

@@ -166,11 +166,14 @@ class Arena:
 class StepWorkspace:
     """All activations / partial-sum slabs of one step, allocated once per (B, shape, dtype)."""
 
-    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None):
+    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None, auxk=None):
         """topk (a TopK crosscoder's k): forward() masks G1's activations in place to each row's k largest (one
         cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself.
         batch_topk ((k, weighted) of a BatchTopK crosscoder): instead, to the batch's B * k best pairs (cc_batch_topk,
-        scored with the decoder norms ws.tn when weighted), in the same step form."""
+        scored with the decoder norms ws.tn when weighted), in the same step form.
+        auxk ((k_aux,), the AuxK dead-latent loss of a TopK / BatchTopK trainer): acts, g_recon, g_pre and the fp32
+        reconstruction get 2 B rows and the g_pre column-partial slab twice its rows; the bottom halves are the aux
+        rows (aux activations, g_aux, their g_pre, e^), the top halves what every B-row consumer sees as before."""
         f32 = torch.float32
         self.topk = topk
         self.batch_topk, self.bt_weighted = batch_topk if batch_topk is not None else (None, False)
@@ -178,6 +181,10 @@ class StepWorkspace:
             raise ValueError("topk and batch_topk exclude each other")
         if topk is not None or batch_topk is not None:
             transposed = False
+        elif auxk is not None:
+            raise ValueError("auxk needs topk or batch_topk")
+        self.k_aux = auxk[0] if auxk is not None else None
+        R = 2 * B if auxk is not None else B  # rows of the buffers that carry an aux half
         K = n * d
         self.B, self.n, self.d, self.h, self.K, self.dtype = B, n, d, h, K, dtype
         E = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
@@ -192,7 +199,8 @@ class StepWorkspace:
         self.x_mean = E(K)
         self.norms = E(h, n)
         self.tn = E(h)
-        self.acts = E(B, h, dt=dtype)
+        self.acts_full = E(R, h, dt=dtype)
+        self.acts = self.acts_full[:B]
         # G2 + loss in one pass (decode_loss) when it serves the shape: its row terms come per 64-column
         # block and its b_dec-gradient partials per 128-row group; one storage holds either layout
         self.fused_ncb = ops.decode_loss_ncb(B, h, n, d, dtype) if self.tr else 0
@@ -235,10 +243,12 @@ class StepWorkspace:
         self.acts_colpart, self.l0_part, self.colsum_acts = self._slots[1]
         self.n_l1 = ops.reduce_parts(h)
         self.l1_part = E(self.n_l1)  # per 64-latent block: sum_h colsum_acts[h] * tn[h] (= B * l1)
-        self.recon = E(B, K)
+        self.recon_full = E(R, K)
+        self.recon = self.recon_full[:B]
         nws = ops.decode_ws_floats(B, h, K, dtype)
         self.dec_ws = E(nws) if nws else None  # G2 split-K partials
-        self.g_recon = E(B, K, dt=dtype)
+        self.g_recon_full = E(R, K, dt=dtype)
+        self.g_recon = self.g_recon_full[:B]
         self.g_recon_t = E(K, B, dt=dtype) if self.tr else None
         self.ncb = ops.loss_col_blocks(d)
         rp = E(2 * n * max(self.ncb, self.fused_ncb) * B)
@@ -256,8 +266,22 @@ class StepWorkspace:
         self.scalars = E(ops.loss_scalars_len(B))
         # transposed mode stores g_pre only as g_pre_t [h][B]; ws.g_pre is then its [B][h] view
         self.g_pre_t = E(h, B, dt=dtype) if self.tr else None
-        self.g_pre = self.g_pre_t.t() if self.tr else E(B, h, dt=dtype)
-        self.gpre_colpart = E(ops.col_part_rows(B), h)
+        self.g_pre_full = None if self.tr else E(R, h, dt=dtype)
+        self.g_pre = self.g_pre_t.t() if self.tr else self.g_pre_full[:B]
+        cpr = ops.col_part_rows(B)
+        self.gpre_colpart_full = E(cpr * (R // B), h)
+        self.gpre_colpart = self.gpre_colpart_full[:cpr]
+        if auxk is not None:
+            # the aux halves, and the aux loss's partial slabs, scalars {auxk_loss, den, scale, valid}, the rows'
+            # selected counts, the dead mask the step's selection used and the dead count after the step
+            self.aux_acts, self.ehat, self.g_aux = self.acts_full[B:], self.recon_full[B:], self.g_recon_full[B:]
+            self.g_pre_aux, self.gpre_colpart_aux = self.g_pre_full[B:], self.gpre_colpart_full[cpr:]
+            self.auxk_part = E(ops.auxk_part_floats(B, K))
+            self.auxk_scalars = torch.zeros(4, dtype=f32, device=device)
+            self.aux_row_count = torch.zeros(B, dtype=torch.int32, device=device)
+            self.was_dead = torch.zeros(h, dtype=torch.uint8, device=device)
+            self.dead_count = torch.zeros(1, dtype=torch.int32, device=device)
+        self.aux_active = False  # the last step issued the aux launches
         nw_w = ops.wgrad_parts(h, K, dtype)
         self.inv_norms = E(h, n)
         sizes = [nw_w, nw_w, ops.reduce_parts(h), ops.reduce_parts(K)]
@@ -342,13 +366,16 @@ def decoder_norms(ws, P):
     _decoder_derived(ws, P)
 
 
-def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None):
+def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None,
+            aux=None):
     """Forward + reconstruction-loss gradient.  P: params Arena.  x_in [B, n, d] any of
     fp32/bf16, factor [n] or None.  Leaves losses in ws.scalars / ws.ev*, g_recon ready
     (loss=False: stops at the fp32 reconstruction, for loss_rows / loss_finalize by slices;
     finalize=False: stops after the loss rows, for loss_finalize_with_g3 / loss_finalize_beside).  Where the fused entry
     serves the shape, G2 and the loss rows are one pass (decode_loss_t; no fp32 reconstruction).
-    bt_threshold ((tensor, beta), BatchTopK, the Trainer's): the running threshold the selection folds its T into."""
+    bt_threshold ((tensor, beta), BatchTopK, the Trainer's): the running threshold the selection folds its T into.
+    aux ((since_fired, dead_after), the Trainer's, a workspace built with auxk): the AuxK selection of G1's activations
+    among the dead latents goes into ws.aux_acts, before the main mask overwrites them."""
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     ws.next_slot()
     with _span("prep"):
@@ -370,6 +397,9 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
                            l0_part=ws.l0_part)
         else:
             ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True)
+    if aux is not None:
+        with _span("auxk_rows"):
+            ops.auxk_rows(ws.acts, h, ws.k_aux, aux[0], aux[1], out=ws.aux_acts, row_count=ws.aux_row_count)
     if ws.topk is not None:
         # TopK: the mask in place, before anything else reads the activations; G2, the loss tail, G3 and G4 then see
         # the masked activations, their column sums and the selected count
@@ -645,6 +675,49 @@ def backward(ws, P, G, l1_coeff, l1_grad_weight=1.0, dacts_done=False, clip=None
         return
     ops.reduce_rows(ws.gpre_colpart, ws.gpre_colpart.shape[0], h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
     ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+
+
+def auxk_forward(ws, P, since_fired, h_real, dead_after, auxk_coeff, active, host=None):
+    """The AuxK part of the forward, after G2 and the loss rows (the step's column sums ws.colsum_acts exist) and
+    before the loss tail is forked: the dead update (always; the dead count also into word 10 of `host`, a
+    _hip.MappedHostBuffer), then -- active: forward(aux=...) selected the aux activations -- the aux decode
+    e^ = aux_acts . W_dec and the aux loss with g_aux (auxk_loss also into word 9 of `host`)."""
+    word = (lambda i: host.device_ptr.value + 4 * i) if host is not None else (lambda i: None)
+    with _span("dead_update"):
+        ops.dead_update(ws.colsum_acts, since_fired, h_real, ws.B, dead_after, ws.dead_count, was_dead=ws.was_dead,
+                        host_ptr=word(10))
+    ws.aux_active = bool(active)
+    if not active:
+        return
+    with _span("auxk_decode"):
+        # (cc_decode_fwd(aux_acts, W_dec, NULL, e^) in the main G2's whole-wave / split-K schedule; its workspace is free)
+        ops.decode_partial(ws.aux_acts, P.W_dec_hk, ws.ehat, ws.dec_ws)
+    with _span("auxk_loss"):
+        ops.auxk_loss(ws.recon, P.b_dec_flat, ws.x, ws.ehat, ws.g_aux, ws.auxk_part, ws.auxk_scalars, auxk_coeff,
+                      host_ptr=word(9))
+
+
+def backward_auxk(ws, P, G, l1_coeff, clip):
+    """backward(clip=...) of the batch-major step with the aux rows of an active AuxK step: G3 on the main rows as
+    always, G3 on the aux rows (no L1 term) into the bottom halves, the aux half of g_pre folded into the main half,
+    G4 over the 2 B concatenated rows (acts^T g_recon + aux_acts^T g_aux; the L1 term from the main column sums), G5
+    over the folded rows, and the grad tail over both halves of the g_pre column-partial slab."""
+    B, n, d = ws.B, ws.n, ws.d
+    l1_scale = float(l1_coeff) / B
+    P.wait_pending()
+    dacts_rows(ws, P, l1_coeff, 0, B)
+    with _span("G3_dacts_aux"):
+        ops.dacts_bwd(ws.g_aux, P.W_dec_hk, ws.aux_acts, ws.tn, 0.0, ws.g_pre_aux, colsum_part=ws.gpre_colpart_aux)
+    with _span("add_rows"):
+        ops.add_rows(ws.g_pre, ws.g_pre_aux)
+    with _span("G4_wgrad_dec"):
+        ops.wgrad_dec(ws.acts_full, ws.g_recon_full, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale, G.W_dec_hk,
+                      ws.sq_slice(1), n, d)
+    with _span("G5_wgrad_enc"):
+        ops.wgrad_enc(ws.g_pre, ws.x, G.W_enc_hk, ws.sq_slice(0))
+    ops.grad_tail(ws.gpre_colpart_full, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3), ws.sq,
+                  ws.sq_off, clip, ws.dtype == torch.bfloat16, ws.clip_out, ws.tail_ctr[1:2])
+    ws.clip_ready = True
 
 
 # workgroups of the decoder-half Adam that runs beside the next step's G1 (128 / 192 / 384 / 512 measured

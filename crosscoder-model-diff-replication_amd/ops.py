@@ -714,3 +714,83 @@ def threshold_mask(acts, h, theta, weight=None, out=None, colsum_part=None, l0_p
     check(lib().cc_threshold_mask(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(weight), _ptr(theta), _ptr(out),
                                   _ptr(colsum_part), _ptr(l0_part), _ptr(row_count), _stream(acts)))
     return out
+
+
+# ---------------------------------------------------------------- the AuxK dead-latent loss
+def _rows_ld(t, name):
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be [rows, width] with contiguous rows")
+    return t.shape[0], t.stride(0) if t.stride(0) >= t.shape[1] else t.shape[1]
+
+
+def auxk_rows(acts, h, k_aux, since_fired, dead_after, out, row_count=None):
+    """Each row of acts [B, ld >= h], first h columns, reduced to its k_aux largest positive values among the dead
+    latents only (since_fired [>= h] int64 on the device; dead: since_fired >= dead_after), into `out` (acts' dtype,
+    shape and strides, another buffer): topk_rows with a column predicate (cc_auxk_rows).  row_count int32 [B]:
+    every row's selected count."""
+    B, ld = _rows_ld(acts, "acts")
+    dev = acts.device
+    if out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride() or out.device != dev:
+        raise ValueError("out must have acts' dtype, shape, strides and device")
+    if out.data_ptr() == acts.data_ptr():
+        raise ValueError("out must not be acts")
+    if since_fired.dtype != torch.int64 or since_fired.device != dev or since_fired.dim() != 1 \
+            or since_fired.numel() < h or not since_fired.is_contiguous():
+        raise ValueError(f"since_fired must be a contiguous int64 tensor of at least {h} elements on {dev}")
+    if row_count is not None and (row_count.dtype != torch.int32 or tuple(row_count.shape) != (B,)
+                                  or row_count.device != dev or not row_count.is_contiguous()):
+        raise ValueError(f"row_count must be a contiguous int32 tensor of shape ({B},) on {dev}")
+    check(lib().cc_auxk_rows(_ptr(acts), ld, B, h, dtype_code(acts.dtype), int(k_aux), _ptr(since_fired),
+                             int(dead_after), _ptr(out), _ptr(row_count), _stream(acts)))
+    return out
+
+
+def dead_update(colsum_acts, since_fired, h_real, B, dead_after, count_out, was_dead=None, host_ptr=None):
+    """since_fired [h] int64 <- 0 where colsum_acts [h] fp32 > 0, else + B; count_out (int32 [1]) = the latents
+    below h_real that are dead (>= dead_after) under the new state; was_dead (uint8 [h], optional): the dead mask
+    under the old state; host_ptr (optional): device address of a host-visible int32 word that also receives the
+    count (cc_dead_update)."""
+    h = colsum_acts.numel()
+    dev = colsum_acts.device
+    for name, t, dt in (("colsum_acts", colsum_acts, torch.float32), ("since_fired", since_fired, torch.int64),
+                        ("was_dead", was_dead, torch.uint8)):
+        if t is not None and (t.dtype != dt or tuple(t.shape) != (h,) or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({h},) on {dev}")
+    if count_out.dtype != torch.int32 or count_out.numel() != 1 or count_out.device != dev:
+        raise ValueError(f"count_out must be an int32 tensor of one element on {dev}")
+    check(lib().cc_dead_update(_ptr(colsum_acts), _ptr(since_fired), h, int(h_real), int(B), int(dead_after),
+                               _ptr(was_dead), _ptr(count_out), _vptr(host_ptr), _stream(colsum_acts)))
+
+
+def auxk_part_floats(B, K):
+    return int(lib().cc_auxk_part_floats(B, K))
+
+
+def auxk_loss(recon_f32, b_dec, x, ehat_f32, g_aux, part, scalars, auxk_coeff, host_ptr=None):
+    """The aux loss of ehat_f32 [B, K] (fp32, = aux_acts . W_dec) against e = x - (recon_f32 + b_dec), and
+    g_aux [B, K] (x's dtype) = dtype(2 auxk_coeff / (B den) (ehat - e)) (cc_auxk_loss).  part: fp32
+    [auxk_part_floats(B, K)]; scalars: fp32 [4] <- {auxk_loss, den, scale, valid}; host_ptr (optional): device address
+    of a host-visible fp32 word that also receives auxk_loss."""
+    B, K = x.shape
+    dev = x.device
+    for name, t, dt in (("recon_f32", recon_f32, torch.float32), ("x", x, x.dtype), ("ehat_f32", ehat_f32, torch.float32),
+                        ("g_aux", g_aux, x.dtype)):
+        if t.dtype != dt or tuple(t.shape) != (B, K) or t.device != dev or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({B}, {K}) on {dev}")
+    if b_dec.dtype != x.dtype or b_dec.numel() != K or not b_dec.is_contiguous():
+        raise ValueError(f"b_dec must be a contiguous {x.dtype} tensor of {K} elements")
+    if part.dtype != torch.float32 or part.numel() < auxk_part_floats(B, K) or not part.is_contiguous():
+        raise ValueError(f"part must be a contiguous fp32 tensor of at least {auxk_part_floats(B, K)} elements")
+    if scalars.dtype != torch.float32 or scalars.numel() < 4 or not scalars.is_contiguous():
+        raise ValueError("scalars must be a contiguous fp32 tensor of at least 4 elements")
+    check(lib().cc_auxk_loss(_ptr(recon_f32), _ptr(b_dec), _ptr(x), _ptr(ehat_f32), _ptr(g_aux), _ptr(part),
+                             _ptr(scalars), _vptr(host_ptr), float(auxk_coeff), B, K, dtype_code(x.dtype), _stream(x)))
+
+
+def add_rows(dst, src):
+    """dst = dtype(float(dst) + float(src)) for two [rows, cols] views of the same dtype and row stride
+    (cc_add_rows)."""
+    rows, ld = _rows_ld(dst, "dst")
+    if src.dtype != dst.dtype or src.shape != dst.shape or src.stride() != dst.stride() or src.device != dst.device:
+        raise ValueError("src must have dst's dtype, shape, strides and device")
+    check(lib().cc_add_rows(_ptr(dst), _ptr(src), rows, dst.shape[1], ld, dtype_code(dst.dtype), _stream(dst)))

@@ -287,6 +287,9 @@ class ShardedTrainer:
             raise ValueError("ShardedTrainer does not serve activation='batch_topk': the batch's threshold across "
                              "latent shards needs a collective of its own (an all-reduce of the histograms); train "
                              "BatchTopK crosscoders with Trainer")
+        if cfg.get("auxk_coeff", 0) or getattr(crosscoder, "auxk", None) is not None:
+            raise ValueError("ShardedTrainer does not serve auxk_coeff > 0: the AuxK dead-latent loss belongs to TopK / "
+                             "BatchTopK crosscoders, which train with Trainer")
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)

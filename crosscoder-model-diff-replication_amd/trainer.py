@@ -1,6 +1,7 @@
 """Drop-in `Trainer` (reference: trainer.py:7-82) whose `step()` is the fused HIP step.
 
-`step()` returns the reference's 9-key loss dict.  Per step it issues the fixed launch
+`step()` returns the reference's 9-key loss dict (plus "auxk_loss" and "dead_latents" when cfg["auxk_coeff"] > 0:
+the AuxK dead-latent loss of TopK / BatchTopK crosscoders).  Per step it issues the fixed launch
 sequence of engine.py and reads the 6 loss scalars once, from mapped host memory the loss-tail
 kernel writes directly (the reference does 7 `.item()` syncs).  Adam state (exp_avg / exp_avg_sq, bf16 like the
 reference's) lives in arenas mirroring the parameter arena, exposed through
@@ -103,6 +104,12 @@ class Trainer:
         self._seq = 0
         self._side = None  # stream of the decoder half's Adam (created on the first step)
         self._last_ws = None  # the last step's workspace (its G2 abort word, engine.check_step_abort)
+        # the AuxK dead-latent loss (crosscoder.auxk_options): tokens since each latent fired (int64, kernel h, on the
+        # device, allocated with the first use) and the number of dead latents under that state, which the host knows
+        # without a sync: the step's dead update writes it to mapped host memory with the loss scalars
+        self.auxk = self.crosscoder.auxk
+        self._tsf = None
+        self._dead_count = 0
 
     def lr_lambda(self, step):
         if step < 0.8 * self.total_steps:
@@ -113,6 +120,46 @@ class Trainer:
         if self.step_counter < 0.05 * self.total_steps:
             return self.cfg["l1_coeff"] * self.step_counter / (0.05 * self.total_steps)
         return self.cfg["l1_coeff"]
+
+    def _since_fired(self):
+        if self._tsf is None:
+            cc = self.crosscoder
+            self._tsf = torch.zeros(cc._hp, dtype=torch.int64, device=cc.arena().data.device)
+        return self._tsf
+
+    @property
+    def tokens_since_fired(self):
+        """int64 [dict_size] on the device (AuxK trainers): tokens since each latent last fired; a latent is dead
+        for the next step iff its entry is >= cfg["dead_tokens"].  Settable with a tensor of the same shape (tests,
+        resuming): the setter reads the new dead count back once."""
+        if self.auxk is None:
+            raise ValueError("tokens_since_fired: cfg['auxk_coeff'] is 0 or absent")
+        return self._since_fired()[:self.crosscoder.d_hidden]
+
+    @tokens_since_fired.setter
+    def tokens_since_fired(self, value):
+        cur = self.tokens_since_fired
+        value = torch.as_tensor(value)
+        if tuple(value.shape) != tuple(cur.shape) or value.dtype.is_floating_point or bool((value < 0).any()):
+            raise ValueError(f"tokens_since_fired takes a non-negative integer tensor of shape {tuple(cur.shape)}")
+        cur.copy_(value.to(cur.device, torch.int64))
+        self._dead_count = int((cur >= self.auxk[2]).sum())
+
+    def auxk_state(self):
+        """The last step's AuxK state (synchronises): aux_acts ([batch, dict_size], a view of the step's aux
+        activations; zeros when the step issued no aux launches), dead (bool [dict_size], the dead set the step
+        used), den, auxk_loss and dead_latents (the dead count after the step)."""
+        ws = self._last_ws
+        if self.auxk is None or ws is None:
+            raise ValueError("auxk_state(): no AuxK step has run")
+        torch.cuda.synchronize(ws.x.device)
+        hr = self.crosscoder.d_hidden
+        sc = ws.auxk_scalars.cpu()
+        active = ws.aux_active
+        return {"aux_acts": ws.aux_acts[:, :hr] if active else torch.zeros_like(ws.aux_acts[:, :hr]),
+                "dead": ws.was_dead[:hr].bool(), "row_count": ws.aux_row_count if active else None,
+                "den": float(sc[1]) if active else 0.0, "auxk_loss": float(sc[0]) if active else 0.0,
+                "dead_latents": int(ws.dead_count)}
 
     def _launch_step(self, host, seq):
         """The step's launches; the loss tail writes the scalars to `host` (a _hip.MappedHostBuffer), then `seq`:
@@ -129,16 +176,26 @@ class Trainer:
         # prep, G1, G2 + the loss rows (one pass where decode_loss_t serves the shape)
         # (BatchTopK: the selection's last launch folds the step's threshold score T into the crosscoder's inference
         # threshold -- T at the first step, then beta * threshold + (1 - beta) * T -- on the device, in stream order)
+        # (AuxK: the dead set of this step is the state the last step's dead update left, whose count the host
+        # already holds -- none dead: no aux launch is issued and the backward is the plain one)
+        aux_on = self.auxk is not None and self._dead_count > 0
         engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False,
-                       bt_threshold=(cc.threshold, cc.threshold_beta) if ws.batch_topk is not None else None)
+                       bt_threshold=(cc.threshold, cc.threshold_beta) if ws.batch_topk is not None else None,
+                       aux=(self._since_fired(), self.auxk[2]) if aux_on else None)
         if self.latent_stats is not None:  # (after G2 and the loss rows, before G3; acts is only read from G1 on: this stream's order suffices)
             self.latent_stats.update_from_acts(ws.acts, row0=self.step_counter * self.cfg["batch_size"])
         # the loss scalars: into mapped host memory from the G3 launch (or, where G3 cannot carry the tail, from a
         # launch on the side stream beside G3)
+        if self.auxk is not None:
+            # on this stream before the event the loss tail waits for: its sequence word publishes words 9 and 10 too
+            engine.auxk_forward(ws, P, self._since_fired(), cc.d_hidden, self.auxk[2], self.auxk[0], aux_on, host=host)
         engine.loss_finalize_with_g3(ws, side, host=host, seq=seq)
         l1c = self.get_l1_coeff()
         # clip_grad_norm_(max_norm=1.0), trainer.py:46
-        engine.backward(ws, P, opt.grads, l1c, clip=1.0)
+        if aux_on:
+            engine.backward_auxk(ws, P, opt.grads, l1c, clip=1.0)
+        else:
+            engine.backward(ws, P, opt.grads, l1c, clip=1.0)
         g = opt.param_groups[0]
         opt.t += 1
         b1, b2 = g["betas"]
@@ -147,6 +204,7 @@ class Trainer:
         self.scheduler.step()
         self._last_l1c = l1c
         self._last_ws = ws
+        self._last_aux_on = aux_on
 
     def _side_stream(self):
         # the decoder half of Adam (+ the next step's decoder norms / W_dec^T) runs here, beside the
@@ -197,6 +255,12 @@ class Trainer:
             "explained_variance_A": rounded(s[4], dt),
             "explained_variance_B": rounded(s[5], dt),
         }
+        if self.auxk is not None:
+            auxk_loss = float(self._mapped.f32[9]) if self._last_aux_on else 0.0
+            self._dead_count = int(self._mapped.u32[10])
+            loss_dict["loss"] = loss_dict["loss"] + self.auxk[0] * auxk_loss
+            loss_dict["auxk_loss"] = auxk_loss
+            loss_dict["dead_latents"] = self._dead_count
         self.step_counter += 1
         return loss_dict
 

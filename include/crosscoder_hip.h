@@ -553,6 +553,52 @@ int cc_threshold_mask(const void* acts, int64_t ld, int64_t B, int64_t h, int dt
                       const float* theta, void* acts_out, float* colsum_part, float* l0_part, int32_t* row_count,
                       void* stream);
 
+/* ---- the AuxK dead-latent loss (TopK / BatchTopK training; Gao et al.'s auxiliary loss) ----
+ * since_fired [h] (int64, device): tokens since each latent last fired.  A latent is dead iff its count is
+ * >= dead_after.
+ *
+ * cc_auxk_rows: cc_topk_rows with a column predicate -- an element's key is 0 (ineligible) unless
+ * since_fired[latent] >= dead_after; otherwise the same eligibility (> 0 on the bits), the same order (larger first,
+ * ties to the smaller latent) and the same limits.  aux_out [B][ld] (must not be acts): each row's first
+ * min(k_aux, #eligible dead) elements keep their bits, the other of the h columns become +0; columns >= h are not
+ * touched; acts is not modified.  row_count (optional, int32 [B]): every row's selected count.  With every latent
+ * dead aux_out has the bits of cc_topk_rows' acts_out for k = k_aux.  No float atomics, bit-reproducible.
+ * Errors in cc_topk_rows' order: CC_ERR_SHAPE (k_aux < 1, k_aux > h, h or ld not a multiple of 8, ld < h, B < 1),
+ * CC_ERR_NULL (acts, since_fired or aux_out missing, aux_out == acts), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h > 2^17),
+ * CC_ERR_ALIGN (16 bytes: acts, aux_out; 8: since_fired; 4: row_count). */
+int cc_auxk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k_aux, const int64_t* since_fired,
+                 int64_t dead_after, void* aux_out, int32_t* row_count, void* stream);
+
+/* After a step's column sums of the masked activations exist (colsum_acts [h] fp32: a latent fired in the step iff
+ * its entry is > 0, positive terms cannot cancel): since_fired[l] = fired ? 0 : since_fired[l] + B for l < h, and
+ * *count_out (device int32) = the number of latents l < h_real that are dead under the NEW state (the padding
+ * latents h_real..h-1 never fire and are not counted).  was_dead (optional, uint8 [h]): 1 where the latent was
+ * dead under the OLD state (the dead set the step's cc_auxk_rows used).  host_out (optional): one int32 word of
+ * host-visible memory (e.g. mapped pinned) that also receives the count, released at system scope.  One small
+ * launch (one workgroup, a fixed-order block reduction).  h <= 2^17. */
+int cc_dead_update(const float* colsum_acts, int64_t* since_fired, int64_t h, int64_t h_real, int64_t B,
+                   int64_t dead_after, uint8_t* was_dead, int32_t* count_out, int32_t* host_out, void* stream);
+
+/* The aux loss and its gradient w.r.t. the aux reconstruction.  With r = recon_f32 + b_dec (the main
+ * reconstruction, fp32 [B][K] and dtype [K]), e = x - r (a constant) and ehat_f32 = aux_acts . W_dec (fp32 [B][K],
+ * no bias):  num = (1/B) sum (ehat - e)^2,  den = (1/B) sum (e - mean_b e)^2 formed as
+ * (sum e^2 - sum_k colsum_k^2 / B) / B,  auxk_loss = num / den, forced to 0 when den is not > 0 or the quotient is
+ * not finite.  scalars [4] (fp32, device) = {auxk_loss, den, scale, valid} with scale = 2 auxk_coeff / (B den)
+ * (0 when forced); host_out (optional): one fp32 word of host-visible memory that also receives auxk_loss.
+ * g_aux [B][K] (dtype) = dtype(scale * (ehat - e)), all +0 when the loss was forced to 0.
+ * Four launches on `stream`: a pass writing per-row-block partial slabs (column sums of e, sum (ehat - e)^2,
+ * sum e^2) into `part` (cc_auxk_part_floats(B, K) floats), the squared column sums and a one-workgroup finaliser
+ * in fp64, and the g_aux pass reading the device-resident scale: fixed order, no float atomics, no host read.
+ * K % 8 == 0. */
+int64_t cc_auxk_part_floats(int64_t B, int64_t K);
+int cc_auxk_loss(const float* recon_f32, const void* b_dec, const void* x, const float* ehat_f32, void* g_aux,
+                 float* part, float* scalars, float* host_out, float auxk_coeff, int64_t B, int64_t K, int dtype,
+                 void* stream);
+
+/* dst[r][c] = dtype(float(dst[r][c]) + float(src[r][c])) over rows x cols elements of two [rows][ld] buffers
+ * (cols, ld % 8 == 0; 16-byte aligned; dst and src distinct): folds the aux half of g_pre into the main half. */
+int cc_add_rows(void* dst, const void* src, int64_t rows, int64_t cols, int64_t ld, int dtype, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
