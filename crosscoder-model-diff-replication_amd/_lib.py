@@ -134,6 +134,10 @@ SIGNATURES = {
     "cc_auxk_part_floats": (_i64, [_i64, _i64]),
     "cc_auxk_loss": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _f, _i64, _i64, _i, _p]),
     "cc_add_rows": (_i, [_p, _p, _i64, _i64, _i64, _i, _p]),
+    "cc_jumprelu_part_rows": (_i64, [_i64, _i64]),
+    "cc_jumprelu_l0_parts": (_i64, [_i64, _i64]),
+    "cc_jumprelu_mask": (_i, [_p, _i64, _i64, _i64, _i, _p, _f, _p, _p, _p, _p, _p]),
+    "cc_jumprelu_bwd": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _f, _f, _p, _p, _p]),
 }
 
 _lib = None

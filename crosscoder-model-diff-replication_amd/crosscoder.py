@@ -59,7 +59,7 @@ def write_checkpoint(state_dict, cfg, save_dir=None, version=0):
     return save_dir, version + 1
 
 
-ACTIVATIONS = ("relu", "topk", "batch_topk")
+ACTIVATIONS = ("relu", "topk", "batch_topk", "jumprelu")
 TOPK_WEIGHTS = ("decoder_norm", "none")
 
 
@@ -68,11 +68,15 @@ def activation_of(cfg):
     reference's and the default, or "topk" -- each row keeps its cfg["k"] largest positive pre-activations
     (ties: the smaller latent), the rest are zero -- which needs cfg["k"], an int in 1..dict_size; or "batch_topk"
     -- the batch keeps its rows * cfg["k"] best (row, latent) pairs, so k is the mean number kept per row -- with
-    the optional keys of batch_topk_options."""
+    the optional keys of batch_topk_options; or "jumprelu" -- an activation is kept iff it exceeds its latent's
+    learned threshold -- with the keys of jumprelu_options (no k)."""
     act = cfg.get("activation", "relu")
     if act not in ACTIVATIONS:
         raise ValueError(f"cfg['activation'] must be one of {ACTIVATIONS}, got {act!r}")
     if act == "relu":
+        return act, None
+    if act == "jumprelu":
+        jumprelu_options(cfg)
         return act, None
     k = cfg.get("k")
     if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= cfg["dict_size"]:
@@ -96,6 +100,30 @@ def batch_topk_options(cfg):
     return weight, float(beta)
 
 
+def _finite_number(v):
+    return not isinstance(v, bool) and isinstance(v, (int, float)) and v == v and abs(v) != float("inf")
+
+
+def jumprelu_options(cfg):
+    """(l0_coeff, jump_bandwidth, jump_threshold_init) of a "jumprelu" cfg: cfg["l0_coeff"], required, a finite float
+    >= 0: the weight of the L0 penalty (the mean number of kept activations per row) in the objective
+    l2 + l1_coeff l1 + l0_coeff l0, warmed up like l1_coeff; cfg["jump_bandwidth"], a finite float > 0 (default 1e-3):
+    the width eps of the straight-through estimators' window around each threshold; cfg["jump_threshold_init"], a
+    finite float (default 1e-3): every latent's threshold at construction (<= 0: that latent starts as plain ReLU)."""
+    if "l0_coeff" not in cfg:
+        raise ValueError("activation 'jumprelu' needs cfg['l0_coeff'], a float >= 0: the weight of its L0 penalty")
+    l0c = cfg["l0_coeff"]
+    if not _finite_number(l0c) or l0c < 0:
+        raise ValueError(f"cfg['l0_coeff'] must be a finite float >= 0, got {l0c!r}")
+    eps = cfg.get("jump_bandwidth", 1e-3)
+    if not _finite_number(eps) or not eps > 0 or not float(torch.tensor(eps, dtype=torch.float32)) > 0:
+        raise ValueError(f"cfg['jump_bandwidth'] must be a finite float > 0 (in fp32), got {eps!r}")
+    init = cfg.get("jump_threshold_init", 1e-3)
+    if not _finite_number(init):
+        raise ValueError(f"cfg['jump_threshold_init'] must be a finite float, got {init!r}")
+    return float(l0c), float(eps), float(init)
+
+
 def auxk_options(cfg, n_models=2):
     """(auxk_coeff, k_aux, dead_tokens) of a cfg, or None when the AuxK dead-latent loss is off (framework extension;
     the keys travel in the checkpoint's cfg json).  cfg["auxk_coeff"]: a float >= 0, absent or 0: off.  On, it needs
@@ -111,6 +139,10 @@ def auxk_options(cfg, n_models=2):
     if cfg.get("activation", "relu") == "relu":
         raise ValueError("cfg['auxk_coeff'] > 0 needs activation 'topk' or 'batch_topk': a ReLU crosscoder's latents "
                          "get gradient whenever they are positive")
+    if cfg.get("activation", "relu") == "jumprelu":
+        raise ValueError("cfg['auxk_coeff'] > 0 is not served with activation 'jumprelu': the aux rows would need a "
+                         "threshold gradient of their own, and a JumpReLU latent is revived by its threshold falling; "
+                         "use 'topk' or 'batch_topk'")
     h = cfg["dict_size"]
     k_aux = cfg.get("k_aux", min(h, max(1, n_models * cfg["d_in"] // 2)))
     if isinstance(k_aux, bool) or not isinstance(k_aux, int) or not 1 <= k_aux <= h:
@@ -151,6 +183,13 @@ class CrossCoder(nn.Module):
             # the inference threshold on the score: the running mean of the training batches' threshold scores
             # (Trainer.step); -1: unset.  Saved and loaded with the state dict (BatchTopK crosscoders only)
             self.register_buffer("threshold", torch.tensor(-1.0, dtype=torch.float32, device=device))
+        if self.activation == "jumprelu":
+            # one learned fp32 threshold per latent (JumpReLU crosscoders only: the other activations' state dicts keep
+            # their keys); the kernels read the kernel-h buffer, whose padding latents never fire
+            self.l0_coeff, self.jump_bandwidth, init = jumprelu_options(cfg)
+            self._theta_buf = torch.zeros(self._hp, dtype=torch.float32, device=device)
+            self._theta_buf[:d_hidden] = init
+            self.jump_threshold = nn.Parameter(self._theta_buf[:d_hidden])
         self._thr_set = None  # (threshold's version when it was read as set): encode then skips the host read
         self._sel_w = None  # (key, tensor): the selection weights of the W_dec they were computed from
         self.d_hidden = d_hidden
@@ -218,6 +257,19 @@ class CrossCoder(nn.Module):
             self._ws = None
         return self._arena
 
+    def theta(self):
+        """fp32 [kernel h] on the arena's device: the JumpReLU thresholds as the kernels read them, of which the
+        parameter jump_threshold is the first dict_size; re-packed if something (e.g. .to()) replaced the parameter."""
+        p, dev = self._parameters["jump_threshold"], self.arena().data.device
+        if p.data_ptr() != self._theta_buf.data_ptr() or p.device != dev or p.dtype != torch.float32:
+            buf = torch.zeros(self._hp, dtype=torch.float32, device=dev)
+            buf[:self.d_hidden] = p.data.to(dev, torch.float32)
+            grad = p.grad
+            self._theta_buf = buf
+            self.jump_threshold = nn.Parameter(buf[:self.d_hidden])
+            self._parameters["jump_threshold"].grad = grad
+        return self._theta_buf
+
     def _workspace(self, B, step=False):
         """The cached step workspace for batch size B.  A workspace that a get_losses() graph still
         needs for its backward (ws.busy) is never reused: the next call gets a fresh one, which is
@@ -231,7 +283,8 @@ class CrossCoder(nn.Module):
                                       topk=self.k if self.activation == "topk" else None,
                                       batch_topk=(self.k, self.topk_weight != "none")
                                       if self.activation == "batch_topk" else None,
-                                      auxk=(self.auxk[1],) if self.auxk is not None else None)
+                                      auxk=(self.auxk[1],) if self.auxk is not None else None,
+                                      jumprelu=self.jump_bandwidth if self.activation == "jumprelu" else None)
             self._ws = ws
         return ws
 
@@ -266,9 +319,11 @@ class CrossCoder(nn.Module):
 
     def activate_(self, acts, use_threshold=None):
         """The crosscoder's sparsifying activation on acts [rows, kernel h] = relu(pre), in place: nothing (ReLU), each
-        row's k largest positive values (TopK; the padding latents are 0), or the BatchTopK selection / threshold
-        mask under selection_weights() (see encode)."""
-        if self.activation == "topk":
+        row's k largest positive values (TopK; the padding latents are 0), the BatchTopK selection / threshold
+        mask under selection_weights() (see encode), or the values above their latent's threshold (JumpReLU)."""
+        if self.activation == "jumprelu":
+            ops.jumprelu_mask(acts, self._hp, self.theta(), self.jump_bandwidth, out=acts)
+        elif self.activation == "topk":
             ops.topk_rows(acts, self._hp, self.k, out=acts)
         elif self.activation == "batch_topk":
             if use_threshold is None:
@@ -369,7 +424,8 @@ class CrossCoder(nn.Module):
 
     def get_losses(self, x):
         """Same LossOutput as crosscoder.py:96-130; differentiable w.r.t. the four params
-        (backward runs the fused HIP backward kernels)."""
+        (backward runs the fused HIP backward kernels).  A JumpReLU crosscoder's thresholds get no gradient here:
+        Trainer.step is what trains them."""
         a = self.arena()
         return LossOutput(*_LossFn.apply(self, x, a.data, self.W_enc, self.W_dec, self.b_enc, self.b_dec))
 
@@ -387,6 +443,12 @@ class CrossCoder(nn.Module):
             state_dict = OrderedDict(state_dict, threshold=self.threshold.detach().clone())
             if meta is not None:
                 state_dict._metadata = meta
+        # likewise a JumpReLU crosscoder: its thresholds then stay what they are
+        if self.activation == "jumprelu" and "jump_threshold" not in state_dict:
+            meta = getattr(state_dict, "_metadata", None)
+            state_dict = OrderedDict(state_dict, jump_threshold=self.jump_threshold.detach().clone())
+            if meta is not None:
+                state_dict._metadata = meta
         return super().load_state_dict(state_dict, *args, **kwargs)
 
     # ------------------------------------------------------------------ checkpoints
@@ -400,13 +462,17 @@ class CrossCoder(nn.Module):
     def save(self):
         if self.save_dir is None:
             self.create_save_dir()
-        self.save_dir, self.save_version = write_checkpoint(self.reference_state_dict(), self.cfg, self.save_dir,
-                                                            self.save_version)
+        sd = self.reference_state_dict()
+        if self.activation == "jumprelu":  # (the checkpoint carries the thresholds; reference_state_dict does not)
+            sd["jump_threshold"] = self.jump_threshold.detach().clone()
+        self.save_dir, self.save_version = write_checkpoint(sd, self.cfg, self.save_dir, self.save_version)
 
     def reference_state_dict(self):
         """state_dict() in the reference's own tensor layout: the views themselves, or -- when the kernel
         dims are padded -- compact copies with the reference strides (W_enc [n, d, h] strides (d, 1, n*d))."""
         sd = self.state_dict()
+        if "jump_threshold" in sd:  # (a JumpReLU crosscoder's fifth parameter is not the reference's)
+            sd = type(sd)((k, v) for k, v in sd.items() if k != "jump_threshold")
         if not self._arena.padded:
             return sd
         out = type(sd)()
@@ -464,7 +530,8 @@ class _LossFn(torch.autograd.Function):
         cc._check_x(x)
         ws = cc._workspace(x.shape[0])
         a = cc.arena()
-        engine.forward(ws, a, cc.pad_input(x).contiguous(), None)
+        engine.forward(ws, a, cc.pad_input(x).contiguous(), None,
+                       theta=cc.theta() if cc.activation == "jumprelu" else None)
         s = ws.scalars
         dt = cc.dtype
         out = (s[0].clone(), s[1].to(dt, copy=True), s[2].clone(), ws.ev.clone(), ws.ev_a.to(dt, copy=True),

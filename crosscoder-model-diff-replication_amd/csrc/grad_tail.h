@@ -68,16 +68,23 @@ CC_DEV void reduce_rows_phase2(const RedSeg& a, int blk, int t, float (*red)[RED
 CC_DEV float bf16r(float f) { return bf2f(f2bf(f)); }
 
 // clip_grad_norm_'s scalar arithmetic (torch/nn/utils/clip_grad.py): a parameter's norm from its squared sum
-// (bf16-rounded as torch._foreach_norm on bf16 returns bf16), then the total norm and the coefficient
-CC_DEV float clip_param_norm(double sq, int emulate_bf16) {
+// (bf16-rounded as torch._foreach_norm on bf16 returns bf16), then the total norm and the coefficient.
+// emulate_bf16 = 2 (CLIP_EMULATE_MIXED): torch on four bf16 gradients followed by fp32 ones -- the norms of the first
+// four are bf16, the stack promotes to fp32, and the total and the coefficient stay fp32
+constexpr int CLIP_EMULATE_MIXED = 2;
+CC_DEV float clip_param_norm(double sq, int emulate_bf16, int p = 0) {
   const float nr = (float)sqrt(sq);
-  return emulate_bf16 ? bf16r(nr) : nr;
+  return emulate_bf16 == CLIP_EMULATE_MIXED ? (p < 4 ? bf16r(nr) : nr) : emulate_bf16 ? bf16r(nr) : nr;
 }
 CC_DEV float clip_coef(const float* norms, int nparams, float max_norm, int emulate_bf16, float& total) {
   float s = 0.f;
-  for (int p = 0; p < nparams; ++p) s += norms[p] * norms[p];
+  // (the mixed list: torch groups the gradients by dtype and stacks the groups' norms with the fp32 group first --
+  // the order its device-and-dtype grouping yields for that list -- so the fp32 sum of squares runs in that order)
+  if (emulate_bf16 == CLIP_EMULATE_MIXED)
+    for (int p = 4; p < nparams; ++p) s += norms[p] * norms[p];
+  for (int p = 0; p < (emulate_bf16 == CLIP_EMULATE_MIXED && nparams > 4 ? 4 : nparams); ++p) s += norms[p] * norms[p];
   total = sqrtf(s);
-  if (emulate_bf16) {
+  if (emulate_bf16 && emulate_bf16 != CLIP_EMULATE_MIXED) {
     total = bf16r(total);                       // vector_norm(stack(bf16 norms)) -> bf16
     const float den = bf16r(total + 1e-6f);     // bf16 tensor + python scalar
     return fminf(bf16r(max_norm / den), 1.f);
@@ -160,7 +167,7 @@ CC_DEV void clip_finish(const ClipArgs& a, const double* s, double (*red)[NT / 6
     const int p = threadIdx.x;
     double t = 0.0;
     for (int w = 0; w < NT / 64; ++w) t += red[p][w];
-    norms[p] = clip_param_norm(t, a.emulate_bf16);
+    norms[p] = clip_param_norm(t, a.emulate_bf16, p);
   }
   __syncthreads();
   if (threadIdx.x == 0) {

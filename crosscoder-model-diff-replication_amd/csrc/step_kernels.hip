@@ -408,7 +408,7 @@ CC_DEV float adam_coef(const AdamArgs& a) {
     bool aborted = false;  // (a negative squared sum: a rank's step was aborted -- ClipArgs::sums_only writes -inf)
     for (int p = 0; p < a.clip_np; ++p) {
       aborted |= a.clip_sums[p] < 0.f;
-      norms[p] = clip_param_norm((double)a.clip_sums[p], a.clip_emulate);
+      norms[p] = clip_param_norm((double)a.clip_sums[p], a.clip_emulate, p);
     }
     const float c = aborted ? CC_CLIP_ABORTED : clip_coef(norms, a.clip_np, a.clip_max_norm, a.clip_emulate, total);
     if (a.clip_out && blockIdx.x == 0 && threadIdx.x == 0) {

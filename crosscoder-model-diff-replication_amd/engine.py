@@ -166,20 +166,28 @@ class Arena:
 class StepWorkspace:
     """All activations / partial-sum slabs of one step, allocated once per (B, shape, dtype)."""
 
-    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None, auxk=None):
+    def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None, auxk=None,
+                 jumprelu=None):
         """topk (a TopK crosscoder's k): forward() masks G1's activations in place to each row's k largest (one
         cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself.
         batch_topk ((k, weighted) of a BatchTopK crosscoder): instead, to the batch's B * k best pairs (cc_batch_topk,
         scored with the decoder norms ws.tn when weighted), in the same step form.
         auxk ((k_aux,), the AuxK dead-latent loss of a TopK / BatchTopK trainer): acts, g_recon, g_pre and the fp32
         reconstruction get 2 B rows and the g_pre column-partial slab twice its rows; the bottom halves are the aux
-        rows (aux activations, g_aux, their g_pre, e^), the top halves what every B-row consumer sees as before."""
+        rows (aux activations, g_aux, their g_pre, e^), the top halves what every B-row consumer sees as before.
+        jumprelu (a JumpReLU crosscoder's bandwidth eps): forward() masks G1's activations in place to those above
+        their latent's threshold (one cc_jumprelu_mask launch, which also writes ws.gate, G3's mask operand), in the
+        batch-major form; the workspace owns the gate, the backward pass' two slabs (the threshold gradient's partials
+        and g_pre's recomputed column partials) and a fifth segment of ws.sq for the threshold's squared gradient."""
         f32 = torch.float32
         self.topk = topk
         self.batch_topk, self.bt_weighted = batch_topk if batch_topk is not None else (None, False)
         if topk is not None and batch_topk is not None:
             raise ValueError("topk and batch_topk exclude each other")
-        if topk is not None or batch_topk is not None:
+        self.jumprelu = None if jumprelu is None else float(jumprelu)
+        if jumprelu is not None and (topk is not None or batch_topk is not None or auxk is not None):
+            raise ValueError("jumprelu excludes topk, batch_topk and auxk")
+        if topk is not None or batch_topk is not None or jumprelu is not None:
             transposed = False
         elif auxk is not None:
             raise ValueError("auxk needs topk or batch_topk")
@@ -235,6 +243,12 @@ class StepWorkspace:
             self.bt_ws = E(ops.batch_topk_ws_bytes(B, h, dtype, self.bt_weighted), dt=torch.uint8)
             self.bt_info = torch.zeros(4, dtype=torch.int32, device=device)
             self.bt_row_count = torch.zeros(B, dtype=torch.int32, device=device)
+        elif jumprelu is not None:
+            self.n_wave, col_rows = ops.jumprelu_l0_parts(B, h), ops.jumprelu_part_rows(B, h)
+            self.gate = E(B, h, dt=dtype)
+            self.thr_part = E(col_rows, h)
+            self.jr_gpre_colpart = E(col_rows, h)
+            self.theta = None  # the thresholds the last forward masked with (fp32 [h]); the backward's too
         else:
             self.n_wave = ops.wave_parts(B, h) if topk is None else ops.topk_l0_parts(B, h)
             col_rows = ops.col_part_rows(B) if topk is None else ops.topk_part_rows(B, h)
@@ -285,6 +299,8 @@ class StepWorkspace:
         nw_w = ops.wgrad_parts(h, K, dtype)
         self.inv_norms = E(h, n)
         sizes = [nw_w, nw_w, ops.reduce_parts(h), ops.reduce_parts(K)]
+        if jumprelu is not None:
+            sizes.append(ops.reduce_parts(h))  # the thresholds' gradient
         self.sq_off = [0]
         for s in sizes:
             self.sq_off.append(self.sq_off[-1] + s)
@@ -367,7 +383,7 @@ def decoder_norms(ws, P):
 
 
 def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None,
-            aux=None):
+            aux=None, theta=None):
     """Forward + reconstruction-loss gradient.  P: params Arena.  x_in [B, n, d] any of
     fp32/bf16, factor [n] or None.  Leaves losses in ws.scalars / ws.ev*, g_recon ready
     (loss=False: stops at the fp32 reconstruction, for loss_rows / loss_finalize by slices;
@@ -375,7 +391,8 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
     serves the shape, G2 and the loss rows are one pass (decode_loss_t; no fp32 reconstruction).
     bt_threshold ((tensor, beta), BatchTopK, the Trainer's): the running threshold the selection folds its T into.
     aux ((since_fired, dead_after), the Trainer's, a workspace built with auxk): the AuxK selection of G1's activations
-    among the dead latents goes into ws.aux_acts, before the main mask overwrites them."""
+    among the dead latents goes into ws.aux_acts, before the main mask overwrites them.
+    theta (fp32 [h], a workspace built with jumprelu): the thresholds of the JumpReLU mask."""
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     ws.next_slot()
     with _span("prep"):
@@ -392,7 +409,7 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         if ws.tr:
             ops.encode_fwd_t(ws.x, P.W_enc_hk, P.b_enc, ws.acts, ws.acts_t, True, colsum_part=ws.acts_colpart,
                              l0_part=ws.l0_part, mask_bits=ws.mask_bits, tile_ctr=_tile_ctr(ws, 0), pre=x_job)
-        elif ws.topk is None and ws.batch_topk is None:
+        elif ws.topk is None and ws.batch_topk is None and ws.jumprelu is None:
             ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True, colsum_part=ws.acts_colpart,
                            l0_part=ws.l0_part)
         else:
@@ -405,6 +422,15 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         # the masked activations, their column sums and the selected count
         with _span("topk"):
             ops.topk_rows(ws.acts, h, ws.topk, out=ws.acts, colsum_part=ws.acts_colpart, l0_part=ws.l0_part)
+    if ws.jumprelu is not None:
+        # JumpReLU: the same, one streaming pass; it also leaves the gate (the kept elements plus the lower half of the
+        # straight-through window), G3's mask operand
+        if theta is None:
+            raise ValueError("a jumprelu workspace's forward needs theta")
+        ws.theta = theta
+        with _span("jumprelu"):
+            ops.jumprelu_mask(ws.acts, h, theta, ws.jumprelu, out=ws.acts, gate=ws.gate, colsum_part=ws.acts_colpart,
+                              l0_part=ws.l0_part)
     norms_done = False
     if ws.batch_topk is not None:
         # BatchTopK: the same, one selection over the batch.  Weighted, it is scored with the decoder norms ws.tn (the
@@ -616,18 +642,24 @@ def dacts_rows(ws, P, l1_coeff, r0, r1, l1_grad_weight=1.0):
                             colsum_part=ws.gpre_colpart[c0:c1], mask_bits=ops.mask_bits_rows(ws.mask_bits, ws.h, r0, r1),
                             tile_ctr=_tile_ctr(ws, 1), tail=tail)
         else:
-            ops.dacts_bwd(ws.g_recon[r0:r1], P.W_dec_hk, ws.acts[r0:r1], ws.tn, l1_scale, ws.g_pre[r0:r1],
+            mask = ws.acts if ws.jumprelu is None else ws.gate
+            ops.dacts_bwd(ws.g_recon[r0:r1], P.W_dec_hk, mask[r0:r1], ws.tn, l1_scale, ws.g_pre[r0:r1],
                           colsum_part=ws.gpre_colpart[c0:c1])
 
 
 def backward(ws, P, G, l1_coeff, l1_grad_weight=1.0, dacts_done=False, clip=None, sums_out=None, zero_mask=0,
-             tail_done=None):
+             tail_done=None, l0_coeff=0.0, theta_grad=None):
     """Gradients of l2 + l1_coeff * l1 into the grads Arena G (+ squared-sum partials).
     dacts_done: G3 already ran per batch slice (dacts_rows).  tail_done: the event of a loss tail
     running beside (loss_finalize_beside), waited for before G4.  clip (max_norm, single-GPU step): the
     bias-gradient sums and clip_grad_norm_'s coefficient in one launch (clip_and_adam then skips
     its clip_finalize).  sums_out (latent-sharded step): instead, the per-parameter squared sums in
-    the same launch (segment_sums semantics, zero_mask), for the all-reduce."""
+    the same launch (segment_sums semantics, zero_mask), for the all-reduce.
+    A jumprelu workspace: backward_jumprelu (l0_coeff, theta_grad: its arguments)."""
+    if ws.jumprelu is not None:
+        if dacts_done or sums_out is not None or l1_grad_weight != 1.0:
+            raise ValueError("the JumpReLU step has no sliced or sharded form")
+        return backward_jumprelu(ws, P, G, l1_coeff, l0_coeff, theta_grad, clip, tail_done)
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     l1_scale = float(l1_coeff) * l1_grad_weight / B
     # (a deferred decoder-half Adam launch of the last step reads the clip coefficient this launch rewrites)
@@ -675,6 +707,48 @@ def backward(ws, P, G, l1_coeff, l1_grad_weight=1.0, dacts_done=False, clip=None
         return
     ops.reduce_rows(ws.gpre_colpart, ws.gpre_colpart.shape[0], h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
     ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+
+
+def backward_jumprelu(ws, P, G, l1_coeff, l0_coeff=0.0, theta_grad=None, clip=None, tail_done=None):
+    """backward() of the batch-major step of a JumpReLU crosscoder, for l2 + l1_coeff l1 + l0_coeff l0: G3 with the gate
+    as its mask operand (it leaves dL/d acts at the kept elements and in the lower half of the window); one pass
+    (cc_jumprelu_bwd) that forms the threshold gradient's partials from the window, zeroes g_pre where gated but not
+    kept and recomputes g_pre's column partials; the reduce that gives theta_grad (fp32 [h]) and segment 4 of ws.sq;
+    then G4G5 and the grad tail as always, the tail over the recomputed column partials and -- theta_grad given --
+    five parameters.  theta_grad None (get_losses' autograd, which serves the four reference parameters): the pass
+    only restores the straight-through g_pre, and the clip is over four."""
+    B, n, d, h = ws.B, ws.n, ws.d, ws.h
+    l1_scale = float(l1_coeff) / B
+    P.wait_pending()
+    dacts_rows(ws, P, l1_coeff, 0, B)
+    with _span("jumprelu_bwd"):
+        ops.jumprelu_bwd(ws.g_pre, ws.gate, h, ws.theta, ws.jumprelu, float(l0_coeff) / B,
+                         gpre_colsum_part=ws.jr_gpre_colpart, thr_part=ws.thr_part if theta_grad is not None else None)
+    if theta_grad is not None:
+        with _span("theta_grad"):
+            ops.reduce_rows(ws.thr_part, ws.thr_part.shape[0], h, out_t=theta_grad, sq_part=ws.sq_slice(4))
+    if tail_done is not None:
+        tail_done.wait(torch.cuda.current_stream(ws.x.device))
+    with _span("G4G5_wgrad"):
+        ops.wgrad_both(ws.acts, ws.g_recon, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale, G.W_dec_hk,
+                       ws.sq_slice(1), ws.g_pre, ws.x, G.W_enc_hk, ws.sq_slice(0), n, d)
+    off = ws.sq_off if theta_grad is not None else ws.sq_off[:5]
+    if clip is not None:
+        ops.grad_tail(ws.jr_gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3),
+                      ws.sq, off, clip, clip_emulation(ws, len(off) - 1), ws.clip_out, ws.tail_ctr[1:2])
+        ws.clip_ready = True
+        return
+    ops.reduce_rows(ws.jr_gpre_colpart, ws.jr_gpre_colpart.shape[0], h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
+    ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, ws.K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+
+
+def clip_emulation(ws, nparams=4):
+    """clip_finalize / grad_tail's emulate_bf16 for this workspace: torch's bf16 roundings for a bf16 crosscoder's four
+    parameters; with the fp32 threshold as a fifth, torch's arithmetic on that mixed list (bf16 norms of the four,
+    fp32 total and coefficient)."""
+    if ws.dtype != torch.bfloat16:
+        return 0
+    return ops.CLIP_EMULATE_MIXED if nparams > 4 else 1
 
 
 def auxk_forward(ws, P, since_fired, h_real, dead_after, auxk_coeff, active, host=None):
@@ -735,27 +809,34 @@ DEC_ADAM_BESIDE_G1 = True
 SERIAL_DEC_BLOCKS = 0  # (0: the library's default grid for the serial form)
 
 
-def clip_and_adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, max_norm=1.0, side_stream=None):
+def clip_and_adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, max_norm=1.0, side_stream=None, extra=None):
     """clip_grad_norm_ (from the squared-sum slabs of the backward) + Adam (see adam())."""
-    emulate = ws.dtype == torch.bfloat16
+    emulate = clip_emulation(ws, len(ws.sq_off) - 1)
     if not ws.clip_ready:
         ops.clip_finalize(ws.sq, ws.sq_off, max_norm, emulate, ws.clip_out)
     ws.clip_ready = False
-    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream)
+    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream, extra=extra)
 
 
-def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sums=None):
+def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sums=None, extra=None):
     """Adam with the clip coefficient in ws.clip_out[0] -- or, clip_sums (sums [4], max_norm): formed in each
     launch from the per-parameter squared gradient sums (cc_adam_step_clip; the encoder-half launch also writes
     ws.clip_out), so no clip launch sits between the sums' all-reduce and Adam.  side_stream: the encoder half runs on torch's
     stream, then the decoder half (+ the next step's decoder norms / W_dec^T) on the side stream, so it
     overlaps the next step's prep / encoder GEMM (G1 reads only the encoder half); P.pending orders every
     later decoder-half use (forward() waits before G2; CrossCoder's accessors, FusedAdam.state and
-    Trainer.synchronize() wait).  Without a side stream: one launch over the whole arena."""
+    Trainer.synchronize() wait).  Without a side stream: one launch over the whole arena.
+    extra ((p, g, m, v), fp32 flat tensors: a JumpReLU crosscoder's thresholds): one more cc_adam_step launch with the
+    same coefficient and hyper-parameters, on torch's stream before anything else."""
     P.wait_pending()  # (no deferred rows of an earlier step may read this step's coefficient)
     P.updates += 1
     coef = ws.clip_out[0:1]
     emulate = ws.dtype == torch.bfloat16
+    if extra is not None:
+        if clip_sums is not None:
+            raise ValueError("extra parameters take the step's own coefficient")
+        with _span("adam_theta"):
+            ops.adam_step(*extra, coef, lr, beta1, beta2, eps, step)
 
     def step_(p, g, m, v, max_blocks=0, clip_out=None):
         if clip_sums is None:

@@ -794,3 +794,58 @@ def add_rows(dst, src):
     if src.dtype != dst.dtype or src.shape != dst.shape or src.stride() != dst.stride() or src.device != dst.device:
         raise ValueError("src must have dst's dtype, shape, strides and device")
     check(lib().cc_add_rows(_ptr(dst), _ptr(src), rows, dst.shape[1], ld, dtype_code(dst.dtype), _stream(dst)))
+
+
+# ---------------------------------------------------------------- JumpReLU (one learned threshold per latent)
+CLIP_EMULATE_MIXED = 2  # clip_finalize / grad_tail's emulate_bf16 for four bf16 gradients followed by fp32 ones
+
+
+def jumprelu_part_rows(B, h):
+    return int(lib().cc_jumprelu_part_rows(B, h))
+
+
+def jumprelu_l0_parts(B, h):
+    return int(lib().cc_jumprelu_l0_parts(B, h))
+
+
+def _jumprelu_args(a, h, theta, same, slabs):
+    B, ld = _rows_ld(a, "acts")
+    dev = a.device
+    for name, t in same:
+        if t is not None and (t.dtype != a.dtype or t.shape != a.shape or t.stride() != a.stride() or t.device != dev):
+            raise ValueError(f"{name} must have acts' dtype, shape, strides and device")
+    if theta.dtype != torch.float32 or tuple(theta.shape) != (h,) or theta.device != dev or not theta.is_contiguous():
+        raise ValueError(f"theta must be a contiguous fp32 tensor of shape ({h},) on {dev}")
+    for name, t in slabs:
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (jumprelu_part_rows(B, h), h)
+                              or t.device != dev or not t.is_contiguous()):
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of shape ({jumprelu_part_rows(B, h)}, {h}) on {dev}")
+    return B, ld
+
+
+def jumprelu_mask(acts, h, theta, eps, out, gate=None, colsum_part=None, l0_part=None):
+    """acts [B, ld >= h] (rows contiguous), first h columns, masked to the elements that are > 0 and > theta[latent]
+    (theta fp32 [h]; strictly) into `out` (may be `acts` itself: in place); gate (optional, another buffer): the
+    elements that are > 0 with a - theta > -eps / 2, which dacts_bwd masks with in a JumpReLU step; colsum_part fp32
+    [jumprelu_part_rows(B, h), h] / l0_part fp32 [jumprelu_l0_parts(B, h)]: column-sum partials and counts of the
+    kept elements (cc_jumprelu_mask).  Returns out."""
+    B, ld = _jumprelu_args(acts, h, theta, (("out", out), ("gate", gate)), (("colsum_part", colsum_part),))
+    if gate is not None and gate.data_ptr() == acts.data_ptr():
+        raise ValueError("gate must not be acts")
+    if l0_part is not None and (l0_part.dtype != torch.float32 or tuple(l0_part.shape) != (jumprelu_l0_parts(B, h),)
+                                or l0_part.device != acts.device or not l0_part.is_contiguous()):
+        raise ValueError(f"l0_part must be a contiguous fp32 tensor of shape ({jumprelu_l0_parts(B, h)},)")
+    check(lib().cc_jumprelu_mask(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(theta), float(eps), _ptr(out),
+                                 _ptr(gate), _ptr(colsum_part), _ptr(l0_part), _stream(acts)))
+    return out
+
+
+def jumprelu_bwd(g_pre, gate, h, theta, eps, l0_scale, gpre_colsum_part=None, thr_part=None):
+    """One pass over g_pre [B, ld >= h] (dacts_bwd's output under `gate`, in/out) and gate (jumprelu_mask's): thr_part
+    fp32 [jumprelu_part_rows(B, h), h] <- partial sums over the window (gated, a - theta < eps / 2) of
+    -(theta / eps) g_pre - l0_scale / eps; g_pre <- +0 where gated but not kept; gpre_colsum_part (same shape) <- the
+    column-sum partials of the resulting g_pre (cc_jumprelu_bwd)."""
+    B, ld = _jumprelu_args(g_pre, h, theta, (("gate", gate),),
+                           (("gpre_colsum_part", gpre_colsum_part), ("thr_part", thr_part)))
+    check(lib().cc_jumprelu_bwd(_ptr(g_pre), _ptr(gate), ld, B, h, dtype_code(g_pre.dtype), _ptr(theta), float(eps),
+                                float(l0_scale), _ptr(gpre_colsum_part), _ptr(thr_part), _stream(g_pre)))

@@ -287,6 +287,10 @@ class ShardedTrainer:
             raise ValueError("ShardedTrainer does not serve activation='batch_topk': the batch's threshold across "
                              "latent shards needs a collective of its own (an all-reduce of the histograms); train "
                              "BatchTopK crosscoders with Trainer")
+        if cfg.get("activation", "relu") == "jumprelu" or getattr(crosscoder, "activation", "relu") == "jumprelu":
+            raise ValueError("ShardedTrainer does not serve activation='jumprelu': the thresholds would shard with the "
+                             "latents, but the sharded step has no threshold gradient, no fifth clip segment and no "
+                             "Adam launch for them yet; train JumpReLU crosscoders with Trainer")
         if cfg.get("auxk_coeff", 0) or getattr(crosscoder, "auxk", None) is not None:
             raise ValueError("ShardedTrainer does not serve auxk_coeff > 0: the AuxK dead-latent loss belongs to TopK / "
                              "BatchTopK crosscoders, which train with Trainer")

@@ -1,7 +1,8 @@
 """Drop-in `Trainer` (reference: trainer.py:7-82) whose `step()` is the fused HIP step.
 
 `step()` returns the reference's 9-key loss dict (plus "auxk_loss" and "dead_latents" when cfg["auxk_coeff"] > 0:
-the AuxK dead-latent loss of TopK / BatchTopK crosscoders).  Per step it issues the fixed launch
+the AuxK dead-latent loss of TopK / BatchTopK crosscoders; plus "l0_coeff" for a JumpReLU
+crosscoder, whose "loss" includes l0_coeff * l0_loss and whose thresholds the step trains).  Per step it issues the fixed launch
 sequence of engine.py and reads the 6 loss scalars once, from mapped host memory the loss-tail
 kernel writes directly (the reference does 7 `.item()` syncs).  Adam state (exp_avg / exp_avg_sq, bf16 like the
 reference's) lives in arenas mirroring the parameter arena, exposed through
@@ -23,6 +24,11 @@ def reference_loss(l2, l1, l1c, dtype):
     return t.item()
 
 
+def jumprelu_loss(loss, l0, l0c):
+    """A JumpReLU step's logged "loss": reference_loss plus l0_coeff * l0_loss, l0 an fp32 0-dim tensor like l2."""
+    return (torch.tensor(loss, dtype=torch.float32) + l0c * torch.tensor(l0, dtype=torch.float32)).item()
+
+
 def rounded(v, dtype):
     """float(v) rounded to the parameter dtype (the reference's param-dtype loss tensors, crosscoder.py:115-126)."""
     return float(torch.tensor(v, dtype=dtype)) if dtype != torch.float32 else float(torch.tensor(v))
@@ -37,6 +43,11 @@ class FusedAdam:
         self.exp_avg = a.like()
         self.exp_avg_sq = a.like()
         self.grads = a.like()
+        # a JumpReLU crosscoder's thresholds: fp32 gradient and moments over the kernel h, in every mode
+        self.theta_grad = self.theta_m = self.theta_v = None
+        if cc.activation == "jumprelu":
+            z = lambda: torch.zeros(cc._hp, dtype=torch.float32, device=a.data.device)  # noqa: E731
+            self.theta_grad, self.theta_m, self.theta_v = z(), z(), z()
         self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": 0.0}]
         self.t = 0
 
@@ -48,6 +59,10 @@ class FusedAdam:
         for name in ("W_enc", "W_dec", "b_enc", "b_dec"):
             p = getattr(self.cc, name)
             st[p] = {"step": torch.tensor(float(self.t)), "exp_avg": m[name], "exp_avg_sq": v[name]}
+        if self.theta_m is not None:
+            h = self.cc.d_hidden
+            st[self.cc.jump_threshold] = {"step": torch.tensor(float(self.t)), "exp_avg": self.theta_m[:h],
+                                          "exp_avg_sq": self.theta_v[:h]}
         return st
 
     def zero_grad(self, set_to_none=True):
@@ -121,6 +136,12 @@ class Trainer:
             return self.cfg["l1_coeff"] * self.step_counter / (0.05 * self.total_steps)
         return self.cfg["l1_coeff"]
 
+    def get_l0_coeff(self):
+        """cfg["l0_coeff"] (JumpReLU crosscoders) on get_l1_coeff's warm-up schedule."""
+        if self.step_counter < 0.05 * self.total_steps:
+            return self.cfg["l0_coeff"] * self.step_counter / (0.05 * self.total_steps)
+        return self.cfg["l0_coeff"]
+
     def _since_fired(self):
         if self._tsf is None:
             cc = self.crosscoder
@@ -181,7 +202,8 @@ class Trainer:
         aux_on = self.auxk is not None and self._dead_count > 0
         engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False,
                        bt_threshold=(cc.threshold, cc.threshold_beta) if ws.batch_topk is not None else None,
-                       aux=(self._since_fired(), self.auxk[2]) if aux_on else None)
+                       aux=(self._since_fired(), self.auxk[2]) if aux_on else None,
+                       theta=cc.theta() if ws.jumprelu is not None else None)
         if self.latent_stats is not None:  # (after G2 and the loss rows, before G3; acts is only read from G1 on: this stream's order suffices)
             self.latent_stats.update_from_acts(ws.acts, row0=self.step_counter * self.cfg["batch_size"])
         # the loss scalars: into mapped host memory from the G3 launch (or, where G3 cannot carry the tail, from a
@@ -192,7 +214,13 @@ class Trainer:
         engine.loss_finalize_with_g3(ws, side, host=host, seq=seq)
         l1c = self.get_l1_coeff()
         # clip_grad_norm_(max_norm=1.0), trainer.py:46
-        if aux_on:
+        l0c = None
+        if ws.jumprelu is not None:
+            # JumpReLU: the objective gains l0_coeff * l0, and the thresholds their gradient, their share of the clip
+            # norm and (below) their Adam launch
+            l0c = self.get_l0_coeff()
+            engine.backward(ws, P, opt.grads, l1c, clip=1.0, l0_coeff=l0c, theta_grad=opt.theta_grad)
+        elif aux_on:
             engine.backward_auxk(ws, P, opt.grads, l1c, clip=1.0)
         else:
             engine.backward(ws, P, opt.grads, l1c, clip=1.0)
@@ -200,9 +228,11 @@ class Trainer:
         opt.t += 1
         b1, b2 = g["betas"]
         engine.clip_and_adam(ws, P, opt.grads, opt.exp_avg, opt.exp_avg_sq, g["lr"], b1, b2, g["eps"], opt.t,
-                             side_stream=side)
+                             side_stream=side,
+                             extra=(ws.theta, opt.theta_grad, opt.theta_m, opt.theta_v) if l0c is not None else None)
         self.scheduler.step()
         self._last_l1c = l1c
+        self._last_l0c = l0c
         self._last_ws = ws
         self._last_aux_on = aux_on
 
@@ -261,6 +291,10 @@ class Trainer:
             loss_dict["loss"] = loss_dict["loss"] + self.auxk[0] * auxk_loss
             loss_dict["auxk_loss"] = auxk_loss
             loss_dict["dead_latents"] = self._dead_count
+        if self._last_l0c is not None:
+            l0c = self._last_l0c
+            loss_dict["loss"] = jumprelu_loss(loss_dict["loss"], l0, l0c)
+            loss_dict["l0_coeff"] = l0c
         self.step_counter += 1
         return loss_dict
 

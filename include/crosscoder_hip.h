@@ -325,8 +325,10 @@ int cc_wgrad_both_t(const void* actsT, const void* g_reconT, const void* W_dec, 
 
 /* clip_grad_norm_(params, max_norm) (trainer.py:46; torch/nn/utils/clip_grad.py): per-param
  * norms from the squared-sum partials sq[off[i] .. off[i+1]) (nparams <= 8, off on the HOST),
- * total = ||(norm_i)||, coef = min(1, max_norm / (total + 1e-6)).  emulate_bf16 rounds the
- * intermediate norms/coef to bf16 as torch does for bf16 grads.
+ * total = ||(norm_i)||, coef = min(1, max_norm / (total + 1e-6)).  emulate_bf16 = 1 rounds the
+ * intermediate norms/coef to bf16 as torch does for bf16 grads; emulate_bf16 = 2 is torch on a MIXED list -- four bf16
+ * gradients followed by fp32 ones (a bf16 JumpReLU crosscoder's threshold): the norms i < 4 are rounded to bf16, the
+ * stacked norms (the fp32 ones first, as torch stacks that list), the total and the coefficient are fp32.
  * out[0] = coef, out[1] = total norm, out[2 + i] = norm_i  (fp32, device). */
 int cc_clip_finalize(const float* sq, const int64_t* off, int nparams, float max_norm, int emulate_bf16,
                      float* out, void* stream);
@@ -598,6 +600,43 @@ int cc_auxk_loss(const float* recon_f32, const void* b_dec, const void* x, const
 /* dst[r][c] = dtype(float(dst[r][c]) + float(src[r][c])) over rows x cols elements of two [rows][ld] buffers
  * (cols, ld % 8 == 0; 16-byte aligned; dst and src distinct): folds the aux half of g_pre into the main half. */
 int cc_add_rows(void* dst, const void* src, int64_t rows, int64_t cols, int64_t ld, int dtype, void* stream);
+
+/* ---- JumpReLU crosscoders: f = a * H(a - theta[latent]), one learned fp32 threshold per latent, trained through
+ * straight-through estimators of bandwidth eps (Rajamanoharan et al. 2024) ----
+ * a is an activation as cc_encode_fwd (apply_relu = 1) stores it, theta fp32 [h], eps > 0 finite, half = 0.5f * eps,
+ * d = float(a) - theta[l] (one fp32 subtract).  "a > 0" is cc_topk_rows' rule on the element's bits: sign clear, not
+ * zero, not NaN; +inf and subnormals count.
+ *
+ * cc_jumprelu_mask, one pass over acts [B][ld], first h columns (h % 8 == 0, ld % 8 == 0, ld >= h, h <= 2^17,
+ * B * h <= 2^31):
+ *   acts_out [B][ld]  an element keeps its bits iff a > 0 and float(a) > theta[l] (strictly), else +0; columns >= h
+ *                     are not touched.  acts_out may be acts (in place).  theta[l] <= 0 is plain ReLU for latent l.
+ *   gate_out [B][ld]  (optional; not acts) an element keeps its bits iff a > 0 and d > -half: the kept elements plus
+ *                     the lower half of the straight-through window (a > 0 and -half < d < half).  It is what
+ *                     cc_dacts_bwd masks with in place of acts.  Columns >= h are not touched.
+ *   colsum_part [cc_jumprelu_part_rows(B, h)][h] (optional, fp32): column-sum partials of the kept activations;
+ *                     cc_reduce_rows over them gives sum_b acts.
+ *   l0_part [cc_jumprelu_l0_parts(B, h)] (optional, fp32): kept counts per workgroup (exact integers below 2^24).
+ * cc_jumprelu_bwd, one pass over g_pre [B][ld] (in/out) and gate [B][ld] (cc_jumprelu_mask's), where g_pre is
+ * cc_dacts_bwd's output under the gate, G = dL/d acts (dtype-rounded) at gated elements:
+ *   thr_part [cc_jumprelu_part_rows(B, h)][h] (optional, fp32): partial sums over the window's elements of
+ *                     -(theta[l] / eps) * G - l0_scale / eps (formed in fp64, rounded once), l0_scale = l0_coeff / B;
+ *                     cc_reduce_rows over them gives theta.grad of l2 + l1_coeff l1 + l0_coeff l0.
+ *   g_pre             elements that are gated but not kept become +0 (the straight-through g_pre of the four
+ *                     reference parameters); nothing else is written.
+ *   gpre_colsum_part [cc_jumprelu_part_rows(B, h)][h] (optional, fp32): column-sum partials of the resulting g_pre
+ *                     (-> b_enc.grad; cc_dacts_bwd's own include the gated elements that were dropped).
+ * Streaming kernels in a fixed summation order, no float atomics: two calls on the same input give the same bits in
+ * every output.  Errors, checked in cc_topk_rows' order before any launch: CC_ERR_SHAPE (B < 1, h < 8, h or ld not
+ * a multiple of 8, ld < h, eps not a finite float > 0), CC_ERR_NULL (acts, theta or acts_out missing; g_pre, gate or
+ * theta missing, g_pre == gate), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h > 2^17, B * h > 2^31), CC_ERR_ALIGN (16 bytes:
+ * every [B][ld] buffer, theta and the slabs; 4 bytes: l0_part). */
+int64_t cc_jumprelu_part_rows(int64_t B, int64_t h);
+int64_t cc_jumprelu_l0_parts(int64_t B, int64_t h);
+int cc_jumprelu_mask(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* theta, float eps,
+                     void* acts_out, void* gate_out, float* colsum_part, float* l0_part, void* stream);
+int cc_jumprelu_bwd(void* g_pre, const void* gate, int64_t ld, int64_t B, int64_t h, int dtype, const float* theta,
+                    float eps, float l0_scale, float* gpre_colsum_part, float* thr_part, void* stream);
 
 #pragma GCC visibility pop
 
