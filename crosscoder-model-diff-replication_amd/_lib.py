@@ -42,6 +42,15 @@ class ColsumJob(ctypes.Structure):
     """cc_colsum_job (include/crosscoder_hip.h)"""
     _fields_ = [("part", ctypes.c_void_p), ("rows", ctypes.c_int64), ("cols", ctypes.c_int64), ("ld", ctypes.c_int64),
                 ("scale", ctypes.c_float), ("out", ctypes.c_void_p)]
+
+
+class PrepJob(ctypes.Structure):
+    """cc_prep_job (include/crosscoder_hip.h)"""
+    _fields_ = [("x_in", ctypes.c_void_p), ("in_dtype", ctypes.c_int), ("factor", ctypes.c_void_p),
+                ("factor_dtype", ctypes.c_int), ("x_out", ctypes.c_void_p), ("x_t", ctypes.c_void_p),
+                ("colsum_part", ctypes.c_void_p), ("B", ctypes.c_int64), ("n", ctypes.c_int64), ("d", ctypes.c_int64)]
+
+
 _i64 = ctypes.c_int64
 _i = ctypes.c_int
 _f = ctypes.c_float
@@ -125,6 +134,7 @@ SIGNATURES = {
     "cc_batch_topk": (_i, [_p, _i64, _i64, _i64, _i, _p, _i64, _p, _p, _p, _p, _p, _p, _f, _p, _i64, _p]),
     "cc_threshold_mask": (_i, [_p, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
     "cc_adam_step": (_i, [_p, _p, _p, _p, _i64, _p, _d, _d, _d, _d, _i64, _i64, _i, _p]),
+    "cc_adam_step_prep": (_i, [_p, _p, _p, _p, _i64, _p, _d, _d, _d, _d, _i64, _i, _p, _p]),
     "cc_adam_step_clip": (_i, [_p, _p, _p, _p, _i64, _p, _i, _f, _i, _p, _d, _d, _d, _d, _i64, _i64, _i, _p]),
     "cc_adam_dec_norms": (_i, [_p, _p, _p, _p, _i64, _p, _p, _i, _f, _i, _d, _d, _d, _d, _i64, _i64, _p, _i64, _i64, _i,
                                _p, _p]),

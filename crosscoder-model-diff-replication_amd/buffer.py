@@ -190,6 +190,18 @@ class Buffer(_BufferProtocol):
             self.refresh()
         return out, self.normalisation_factor
 
+    def peek_raw(self):
+        """The (rows, factors) the next next_raw() will return, without advancing -- views of the resident buffer (the
+        fused Trainer preps them ahead, inside the running step) -- or None where that cannot be said: the fp32 batch
+        whose next_raw() refreshes, which aliases rows the refresh overwrites.  (A refresh that the last next_raw()
+        triggered has already happened: these are rows of the refreshed buffer.  Where the next next_raw() refreshes,
+        it returns a copy of these rows.)"""
+        B = self.cfg["batch_size"]
+        p = self.buffer_pointer
+        if p + B > self.buffer.shape[0] // 2 - B and self.buffer.dtype == torch.float32:
+            return None
+        return self.buffer[p: p + B], self.normalisation_factor
+
 
 class SyntheticBuffer(_BufferProtocol):
     """Seeded synthetic residual-stream stand-in: x ~ N(0,1) per model scaled by 1/factor
@@ -224,3 +236,9 @@ class SyntheticBuffer(_BufferProtocol):
         out = self.buffer[self.buffer_pointer: self.buffer_pointer + B]
         self.buffer_pointer += B
         return out, self.normalisation_factor
+
+    def peek_raw(self):
+        """The (rows, factors) the next next_raw() will return, without advancing."""
+        B = self.cfg["batch_size"]
+        p = self.buffer_pointer if self.buffer_pointer + B <= self.buffer.shape[0] else 0
+        return self.buffer[p: p + B], self.normalisation_factor

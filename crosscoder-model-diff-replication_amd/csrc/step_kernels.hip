@@ -30,20 +30,22 @@ CC_DEV void tile_put8(char* lds, int r, int chunk, const float v[8]) {
 }
 // NT: non-temporal stores (prep's x^T: read once, by G5 at the step's end; kept out of the Infinity Cache it leaves
 // room for what the step reads before that -- step -7 us, profiles/r04_ab_epilogue_store_policy.txt)
-template <int R, bool NT = false>
+// (PITCH: bytes of a tile row, 1024 = 512 columns; a narrower tile keeps the chunk swizzle)
+template <int R, bool NT = false, int PITCH = 1024>
 CC_DEV void tile_store_transposed(const char* lds, void* out_t, int64_t ldt, int64_t col0, int ncols, int64_t row0,
                                   int nrows) {
-  constexpr int RQ = R / 32;  // 32-row bands
+  constexpr int RQ = R / 32;      // 32-row bands
+  constexpr int NCG = PITCH / 32;  // 16-column groups
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-  for (int it = wave; it < 32 * RQ; it += 4) {
+  for (int it = wave; it < NCG * RQ; it += 4) {
     const int cg = it / RQ, rb = (it % RQ) * 32 + g * 8;  // 16-column group, first of the lane's 8 rows
     const int ca = cg * 16 + 4 * p, c = cg * 16 + i;
     const int l0 = rb + q, l1 = rb + 4 + q;
     const bf16x4 v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_bf16x4_s*)(lds + l0 * 1024 + (((ca >> 3) ^ (l0 & 7)) << 4) + (ca & 4) * 2));
+        (lds_bf16x4_s*)(lds + l0 * PITCH + (((ca >> 3) ^ (l0 & 7)) << 4) + (ca & 4) * 2));
     const bf16x4 v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-        (lds_bf16x4_s*)(lds + l1 * 1024 + (((ca >> 3) ^ (l1 & 7)) << 4) + (ca & 4) * 2));
+        (lds_bf16x4_s*)(lds + l1 * PITCH + (((ca >> 3) ^ (l1 & 7)) << 4) + (ca & 4) * 2));
     if (c < ncols && rb < nrows) {
       const bf16x8 v = bf16x8{v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
       bf16x8* dst = (bf16x8*)((bf16_t*)out_t + (col0 + c) * ldt + row0 + rb);
@@ -125,6 +127,71 @@ __global__ __launch_bounds__(256) void prep_kernel(const void* __restrict__ x_in
   for (int i = threadIdx.x; i < 512; i += 256) {
     int c = blockIdx.x * 512 + i;
     if (c < K) colsum_part[(int64_t)blockIdx.y * K + c] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
+  }
+}
+
+// prep_kernel<.., CC_BF16, true>'s block of 64 rows, 128 columns wide (grid (ceil(K/128), ceil(B/64))), for the
+// workgroups of the Adam launch that carry the prep (adam_bulk_prep_kernel): 2 rows per thread in registers and an
+// 8 KB tile, so the launch keeps the Adam's 8 workgroups per CU, and x^T still goes out in 64-byte runs (32 rows).
+// lane & 15 -> 8 columns, thread >> 4 -> rows slot, slot + 16 of each half.  The same bits as prep_kernel: the
+// column sums are re-read from the tile (the stored bf16 values are what prep_kernel adds), one (column, row class
+// r % 4) per accumulator, adding rows in prep_kernel's order; the classes are combined as there.
+constexpr int PREPN_COLS = 128, PREPN_LDS = 32 * PREPN_COLS * 2;
+template <int DIN, int DF>
+CC_DEV void prep_block_narrow(char* lds, int bx, int by, const void* __restrict__ x_in,
+                              const void* __restrict__ factor, void* __restrict__ x_out,
+                              float* __restrict__ colsum_part, int B, int n, int d, void* __restrict__ x_t) {
+  constexpr int PITCH = PREPN_COLS * 2;
+  const int K = n * d;
+  const int ch = threadIdx.x & 15, slot = threadIdx.x >> 4;
+  const int col = bx * PREPN_COLS + ch * 8;
+  const int r0 = by * PREP_ROWS;
+  const int scol = threadIdx.x & 127, sw = threadIdx.x >> 7;  // column-sum duty: row classes sw and sw + 2
+  float acc[2] = {0.f, 0.f};
+  float f = 1.f;
+  if (factor && col < K) f = Elem<DF>::load((const typename Elem<DF>::T*)factor + col / d);
+  for (int half = 0; half < 2; ++half) {
+    const int base = r0 + 32 * half;
+    if (base >= B) break;  // block-uniform
+    const int nr = B - base < 32 ? B - base : 32;
+    if (col < K) {
+      float v[2][8];
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+        if (slot + 16 * k < nr) load8<DIN>(x_in, (int64_t)(base + slot + 16 * k) * K + col, v[k]);
+#pragma unroll
+      for (int k = 0; k < 2; ++k) {
+        const int r = slot + 16 * k;
+        if (r >= nr) break;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[k][j] = Elem<CC_BF16>::round(v[k][j] * f);
+        store8<CC_BF16>(x_out, (int64_t)(base + r) * K + col, v[k]);
+        bf16x8 b;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) b[j] = (short)f2bf(v[k][j]);
+        *(bf16x8*)(lds + r * PITCH + ((ch ^ (r & 7)) << 4)) = b;
+      }
+    }
+    __syncthreads();
+    tile_store_transposed<32, true, PITCH>(lds, x_t, B, (int64_t)bx * PREPN_COLS, K - bx * PREPN_COLS, base, nr);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const int r = sw + 2 * c + 4 * k;
+        if (r < nr)
+          acc[c] += bf2f(*(const bf16_t*)(lds + r * PITCH + (((scol >> 3) ^ (r & 7)) << 4) + (scol & 7) * 2));
+      }
+    __syncthreads();
+  }
+  if (!colsum_part) return;
+  float(*red)[PREPN_COLS] = (float(*)[PREPN_COLS])lds;
+  red[sw][scol] = acc[0];
+  red[sw + 2][scol] = acc[1];
+  __syncthreads();
+  if (threadIdx.x < PREPN_COLS) {
+    const int c = bx * PREPN_COLS + threadIdx.x, i = threadIdx.x;
+    if (c < K) colsum_part[(int64_t)by * K + c] = ((red[0][i] + red[1][i]) + red[2][i]) + red[3][i];
   }
 }
 
@@ -701,30 +768,42 @@ constexpr int ADAM_U = 1;
 // pass over the grid (no grid-stride loop).  U = 1 measured fastest (390 us for the 151 M-element
 // config-2 arena = 5.4 TB/s; U = 2: 398 us; the grid-stride loop: 431 us).
 // (LO: the lerp form, chosen by the launcher like adam_pipe_kernel's; bf16 only)
+constexpr bool ADAM_PN = false, ADAM_SN = true;
+// the bf16 form's workgroup `block`: packed, the fast arithmetic (adam_chunk_bf16).  BLOCK_COEF: the coefficient
+// through adam_coef_block (4 bytes of LDS); false: read from a.coef by every thread (no clip_sums)
+template <int U, bool LO, bool BLOCK_COEF = true>
+CC_DEV void adam_bulk_bf16(const AdamArgs& a, int64_t nchunks, int64_t block) {
+  constexpr bool PN = ADAM_PN, SN = ADAM_SN;
+  const int64_t c0 = block * 256 * U + threadIdx.x;
+  bf16x8 p[U], g[U], m[U], v[U];
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t c = c0 + u * 256;
+    if (c < nchunks) {
+      p[u] = ld_bf16x8<PN>(a.p, c * 8); g[u] = ld_bf16x8<SN>(a.g, c * 8); m[u] = ld_bf16x8<SN>(a.m, c * 8);
+      v[u] = ld_bf16x8<SN>(a.v, c * 8);
+    }
+  }
+  float coef;  // (placed as in adam_bulk_kernel's fp32 form)
+  if constexpr (BLOCK_COEF) coef = adam_coef_block(a);
+  else coef = a.coef ? *a.coef : 1.f;
+  if (coef < 0.f) return;
+#pragma unroll
+  for (int u = 0; u < U; ++u) {
+    const int64_t c = c0 + u * 256;
+    if (c < nchunks) {
+      adam_chunk_bf16<LO>(a, coef, c * 8, p[u], g[u], m[u], v[u]);
+      st_bf16x8<PN>(a.p, c * 8, p[u]); st_bf16x8<SN>(a.m, c * 8, m[u]); st_bf16x8<SN>(a.v, c * 8, v[u]);
+    }
+  }
+}
+
 template <int DT, int U, bool LO>
 __global__ __launch_bounds__(256) void adam_bulk_kernel(const AdamArgs a, int64_t nchunks) {
   const int64_t c0 = (int64_t)blockIdx.x * 256 * U + threadIdx.x;
-  constexpr bool PN = false, SN = true;
-  if constexpr (DT == CC_BF16) {  // packed, the fast arithmetic (adam_chunk_bf16)
-    bf16x8 p[U], g[U], m[U], v[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t c = c0 + u * 256;
-      if (c < nchunks) {
-        p[u] = ld_bf16x8<PN>(a.p, c * 8); g[u] = ld_bf16x8<SN>(a.g, c * 8); m[u] = ld_bf16x8<SN>(a.m, c * 8);
-        v[u] = ld_bf16x8<SN>(a.v, c * 8);
-      }
-    }
-    const float coef = adam_coef_block(a);  // (placed as below)
-    if (coef < 0.f) return;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int64_t c = c0 + u * 256;
-      if (c < nchunks) {
-        adam_chunk_bf16<LO>(a, coef, c * 8, p[u], g[u], m[u], v[u]);
-        st_bf16x8<PN>(a.p, c * 8, p[u]); st_bf16x8<SN>(a.m, c * 8, m[u]); st_bf16x8<SN>(a.v, c * 8, v[u]);
-      }
-    }
+  constexpr bool PN = ADAM_PN, SN = ADAM_SN;
+  if constexpr (DT == CC_BF16) {
+    adam_bulk_bf16<U, LO>(a, nchunks, blockIdx.x);
     return;
   }
   float p[U][8], g[U][8], m[U][8], v[U][8];
@@ -749,6 +828,35 @@ __global__ __launch_bounds__(256) void adam_bulk_kernel(const AdamArgs a, int64_
       st8<DT, PN>(a.p, c * 8, p[u]); st8<DT, SN>(a.m, c * 8, m[u]); st8<DT, SN>(a.v, c * 8, v[u]);
     }
   }
+}
+
+// The bf16 bulk Adam whose first workgroups run a cc_prep_input_t (the NEXT batch's x, x^T and column-sum partials:
+// nothing the step computes feeds them, and their previous readers finished before this launch), so the step has no
+// prep launch of its own: blocks [0, prep_blocks) are prep_block_narrow's grid, x fastest (they come first, so
+// they finish under the Adam's stream of traffic), the others adam_bulk_kernel's.  Same bits as the two launches.
+// The Adam's workgroups run 8 to a CU (one 8-element chunk per thread: its bandwidth is its occupancy), so the prep
+// blocks are the narrow form: 60 VGPRs and 8 KB of LDS keep that occupancy.  (prep_kernel's own block in 8-row
+// passes does too, but its 16-byte runs of x^T cost the step 45 us; with its 32-row passes -- 106 VGPRs, 32 KB --
+// the launch measured the same as this form.)
+// An aborted step (coef < 0) applies no update; the prep blocks run regardless (idempotent).
+struct PrepJob {
+  const void* x_in;
+  const void* factor;
+  void* x_out;
+  float* colsum_part;
+  void* x_t;
+  int B, n, d;
+  int gx, blocks;  // prep grid's x extent, and its workgroups
+};
+template <bool LO, int DIN, int DF>
+__global__ __launch_bounds__(256) void adam_bulk_prep_kernel(const AdamArgs a, int64_t nchunks, const PrepJob j) {
+  __shared__ __attribute__((aligned(16))) char lds[PREPN_LDS];
+  if ((int)blockIdx.x < j.blocks) {  // block-uniform
+    prep_block_narrow<DIN, DF>(lds, blockIdx.x % j.gx, blockIdx.x / j.gx, j.x_in, j.factor, j.x_out, j.colsum_part,
+                               j.B, j.n, j.d, j.x_t);
+    return;
+  }
+  adam_bulk_bf16<ADAM_U, LO, false>(a, nchunks, (int64_t)blockIdx.x - j.blocks);
 }
 
 template <int DT, bool LO>
@@ -1336,6 +1444,43 @@ int cc_adam_step_clip(void* p, const void* g, void* m, void* v, int64_t numel, c
   a.clip_max_norm = max_norm;
   a.clip_out = clip_out;
   return adam_launch(a, max_blocks, dtype, (hipStream_t)stream);
+}
+
+int cc_adam_step_prep(void* p, const void* g, void* m, void* v, int64_t numel, const float* coef, double lr,
+                      double beta1, double beta2, double eps, int64_t step, int dtype, const cc_prep_job* prep,
+                      void* stream) {
+  if (!prep)
+    return cc_adam_step(p, g, m, v, numel, coef, lr, beta1, beta2, eps, step, 0, dtype, stream);
+  if (!p || !g || !m || !v || !prep->x_in || !prep->x_out || !prep->x_t) return CC_ERR_NULL;
+  if (dtype != CC_BF16) return CC_ERR_DTYPE;
+  if (numel <= 0 || numel % 8 || step <= 0) return CC_ERR_SHAPE;
+  if (!al16(p) || !al16(g) || !al16(m) || !al16(v)) return CC_ERR_ALIGN;
+  // (cc_prep_input_t's checks)
+  const int64_t B = prep->B, n = prep->n, d = prep->d;
+  if (B <= 0 || n <= 0 || d <= 0 || d % 8 || B % 8 || B > INT32_MAX || n * d > INT32_MAX) return CC_ERR_SHAPE;
+  if (!al16(prep->x_in) || !al16(prep->x_out) || !al16(prep->x_t)) return CC_ERR_ALIGN;
+  if (prep->factor && prep->factor_dtype != CC_BF16 && prep->factor_dtype != CC_F32) return CC_ERR_DTYPE;
+  if (prep->in_dtype != CC_BF16 && prep->in_dtype != CC_F32) return CC_ERR_DTYPE;
+  const AdamArgs a = adam_args(p, g, m, v, numel, coef, lr, beta1, beta2, eps, step);
+  const int64_t nchunks = numel / 8;
+  const int64_t gx = (n * d + PREPN_COLS - 1) / PREPN_COLS, pblocks = gx * cc_prep_part_rows(B);
+  const int64_t blocks = pblocks + (nchunks + 256 * ADAM_U - 1) / (256 * ADAM_U);
+  if (blocks > INT32_MAX) return CC_ERR_SHAPE;
+  const PrepJob j = {prep->x_in, prep->factor, prep->x_out, prep->colsum_part, prep->x_t,
+                     (int)B,     (int)n,       (int)d,      (int)gx,           (int)pblocks};
+  hipStream_t st = (hipStream_t)stream;
+  const bool fb = prep->factor && prep->factor_dtype == CC_BF16;
+#define ADAM_PREP(DI, DF)                                                                                        \
+  ADAM_LO(a, hipLaunchKernelGGL((adam_bulk_prep_kernel<LO_, DI, DF>), dim3((unsigned)blocks), dim3(256), 0, st, a, \
+                                nchunks, j))
+  if (prep->in_dtype == CC_BF16) {
+    if (fb) ADAM_PREP(CC_BF16, CC_BF16); else ADAM_PREP(CC_BF16, CC_F32);
+  } else {
+    if (fb) ADAM_PREP(CC_F32, CC_BF16); else ADAM_PREP(CC_F32, CC_F32);
+  }
+#undef ADAM_PREP
+  CC_LAUNCH_CHECK();
+  return CC_OK;
 }
 
 int64_t cc_adam_capped_blocks(int64_t numel, int64_t max_blocks) {

@@ -15,10 +15,11 @@ every GEMM streams 128-byte rows.
 
 Step (reference trainer.py:41-63 -> crosscoder.py:96-130 -> autograd -> clip -> Adam), single GPU:
   prep      x = dtype(buf * factor), x^T, column sums for x.mean(0)          buffer.py:124, crosscoder.py:99
+            (the Trainer's steady state: carried by the previous step's encoder-half Adam launch, PREP_IN_ADAM)
   G1        (prologue: x.mean(0)) acts = relu(x W_enc + b_enc), acts^T, mask bits, colsum/l0 slabs
                                                                             crosscoder.py:69-80,112,128
-  (rest)    the decoder-half Adam's last rows of the previous step (+ their norm partials), then a wait
-            for the side stream's rows
+  (rest)    the decoder-half Adam's last rows of the previous step (+ their norm partials; none at
+            DEC_SIDE_ROWS = 1.0, where the side launch takes b_dec along), then a wait for the side stream's rows
   G2+loss   (prologue: sum_b acts) acts W_dec + b_dec - x -> l2/tv row terms, g_recon = 2(r-x)/B,
             g_recon^T, db_dec slab (no fp32 reconstruction); its split-K leftover launch also finalises
             ||W_dec[h,m]||, their sum over m and inverses from the Adam's partials
@@ -28,8 +29,8 @@ Step (reference trainer.py:41-63 -> crosscoder.py:96-130 -> autograd -> clip -> 
                                                                             crosscoder.py:106-128, autograd
   G4G5      dW_dec = acts^T g_recon + l1c/B colsum(acts) W_dec/||W_dec||,
             dW_enc = g_pre^T x, db_enc / db_dec, the clip coefficient        autograd, trainer.py:46
-  adam      encoder half on this stream; the decoder half's first rows on the side stream beside the
-            next step's G1 (with the next step's norm partials)              trainer.py:47
+  adam      encoder half on this stream (+ the next batch's prep); the decoder half's first rows on the side
+            stream beside the next step's G1 (with the next step's norm partials)   trainer.py:47
 G1, G3 and G4G5 are persistent launches that hand out their tiles per XCD from counters (DYNAMIC_TILES).
 """
 import contextlib
@@ -64,6 +65,27 @@ LOSS_TAIL_IN_G3 = True
 # waiting for the Adam's event: the ~10 us a cross-stream dependency takes to release the next kernel go away.
 # Other readers still wait for the event.  The same bits either way.
 G2_WAITS_IN_KERNEL = True
+
+
+# The next batch's prep (x, x^T, the column-sum partials) rides in the step's encoder-half Adam launch (its first
+# workgroups; cc_adam_step_prep) where the caller can name that batch (adam's next_batch, the Trainer's
+# buffer.peek_raw()); the next forward() then skips its prep launch if it is handed exactly that batch (ws.prep_token)
+# and runs prep as always otherwise.  The same bits either way.
+PREP_IN_ADAM = True
+
+
+# The side-stream decoder-half Adam takes b_dec along when it takes every row of W_dec (DEC_SIDE_ROWS = 1.0), so the
+# first reader launches nothing after G1: it only waits (in G2's kernel, or for the event).  The same bits either way.
+BDEC_IN_SIDE_ADAM = True
+
+
+def _prep_token(x_in, factor, tag):
+    """What identifies a raw batch handed to forward() as the one an Adam launch already prepped: the storage, layout
+    and version counters of the batch and the factors, the caller's tag (the buffer's refresh count: a refresh rewrites
+    rows without touching a version counter) and the stream both launches run on."""
+    f = None if factor is None else (factor.data_ptr(), factor.dtype, tuple(factor.shape), factor._version)
+    return (x_in.data_ptr(), x_in.dtype, tuple(x_in.shape), x_in.stride(), x_in._version, f, tag,
+            torch.cuda.current_stream(x_in.device).cuda_stream)
 
 
 def _tile_ctr(ws, k):
@@ -322,6 +344,11 @@ class StepWorkspace:
         self.adam_done_target = 0
         self.wait_err = None
         self.norms_token = None
+        # the raw batch whose prep the last Adam launch carried (_prep_token; PREP_IN_ADAM), into a second set of
+        # (x, x_t, x_colpart) allocated with the first such launch: ws.x stays the step's own batch for whoever reads
+        # it after the step.  Any forward() consumes the token; the one handed that batch swaps the two sets
+        self.prep_token = None
+        self.x_next = None
         self.busy = None  # weakref to the token of an autograd graph whose backward still needs this workspace
 
     def next_slot(self):
@@ -383,7 +410,7 @@ def decoder_norms(ws, P):
 
 
 def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None,
-            aux=None, theta=None):
+            aux=None, theta=None, prep_tag=None):
     """Forward + reconstruction-loss gradient.  P: params Arena.  x_in [B, n, d] any of
     fp32/bf16, factor [n] or None.  Leaves losses in ws.scalars / ws.ev*, g_recon ready
     (loss=False: stops at the fp32 reconstruction, for loss_rows / loss_finalize by slices;
@@ -392,11 +419,17 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
     bt_threshold ((tensor, beta), BatchTopK, the Trainer's): the running threshold the selection folds its T into.
     aux ((since_fired, dead_after), the Trainer's, a workspace built with auxk): the AuxK selection of G1's activations
     among the dead latents goes into ws.aux_acts, before the main mask overwrites them.
-    theta (fp32 [h], a workspace built with jumprelu): the thresholds of the JumpReLU mask."""
+    theta (fp32 [h], a workspace built with jumprelu): the thresholds of the JumpReLU mask.
+    prep_tag: the tag of adam's next_batch, where x_in may be that batch (the Trainer's: its buffer's refresh count)."""
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     ws.next_slot()
-    with _span("prep"):
-        ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
+    # (the last Adam launch may have carried exactly this batch's prep: PREP_IN_ADAM)
+    prepped, ws.prep_token = ws.prep_token, None
+    if prepped is not None and prepped == _prep_token(x_in, factor, prep_tag):
+        (ws.x, ws.x_t, ws.x_colpart), ws.x_next = ws.x_next, (ws.x, ws.x_t, ws.x_colpart)
+    else:
+        with _span("prep"):
+            ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
     # G1 reads only the encoder half: it may overlap the previous step's decoder-half Adam.  x.mean(0) (first
     # read by the loss) and sum_b acts (G4's L1 term and the l1 loss, crosscoder.py:112,126): column reductions
     # of the prep / G1 partial slabs -- carried in the prologues of G1 and G2 where the step's fused path runs
@@ -809,16 +842,18 @@ DEC_ADAM_BESIDE_G1 = True
 SERIAL_DEC_BLOCKS = 0  # (0: the library's default grid for the serial form)
 
 
-def clip_and_adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, max_norm=1.0, side_stream=None, extra=None):
+def clip_and_adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, max_norm=1.0, side_stream=None, extra=None,
+                  next_batch=None):
     """clip_grad_norm_ (from the squared-sum slabs of the backward) + Adam (see adam())."""
     emulate = clip_emulation(ws, len(ws.sq_off) - 1)
     if not ws.clip_ready:
         ops.clip_finalize(ws.sq, ws.sq_off, max_norm, emulate, ws.clip_out)
     ws.clip_ready = False
-    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream, extra=extra)
+    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream, extra=extra, next_batch=next_batch)
 
 
-def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sums=None, extra=None):
+def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sums=None, extra=None,
+         next_batch=None):
     """Adam with the clip coefficient in ws.clip_out[0] -- or, clip_sums (sums [4], max_norm): formed in each
     launch from the per-parameter squared gradient sums (cc_adam_step_clip; the encoder-half launch also writes
     ws.clip_out), so no clip launch sits between the sums' all-reduce and Adam.  side_stream: the encoder half runs on torch's
@@ -827,7 +862,10 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
     later decoder-half use (forward() waits before G2; CrossCoder's accessors, FusedAdam.state and
     Trainer.synchronize() wait).  Without a side stream: one launch over the whole arena.
     extra ((p, g, m, v), fp32 flat tensors: a JumpReLU crosscoder's thresholds): one more cc_adam_step launch with the
-    same coefficient and hyper-parameters, on torch's stream before anything else."""
+    same coefficient and hyper-parameters, on torch's stream before anything else.
+    next_batch ((x_in, factor, tag), with a side stream): the raw batch the next forward(ws, ..., prep_tag=tag) will most
+    likely be handed, unchanged until then; where the shapes allow, its prep rides in the encoder half's launch
+    (PREP_IN_ADAM) and that forward launches none.  A forward handed anything else runs its prep as always."""
     P.wait_pending()  # (no deferred rows of an earlier step may read this step's coefficient)
     P.updates += 1
     coef = ws.clip_out[0:1]
@@ -850,8 +888,22 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
             step_(P.data, G.data, M.data, V.data, clip_out=ws.clip_out)
         return
     dev = P.data.device
+    enc = [A.enc_part() for A in (P, G, M, V)]
+    ride = None
+    if (PREP_IN_ADAM and next_batch is not None and clip_sums is None and enc[0].numel() % 8 == 0
+            and tuple(next_batch[0].shape) == (ws.B, ws.n, ws.d) and next_batch[0].device == dev
+            and ops.prep_job_ok(next_batch[0], next_batch[1], ws.dtype, ws.x_t)):
+        ride = _prep_token(*next_batch)
     with _span("adam"):
-        step_(P.enc_part(), G.enc_part(), M.enc_part(), V.enc_part(), clip_out=ws.clip_out)
+        if ride is not None:
+            # (into the second set of prep outputs, whose last readers -- the step before this one -- are long done)
+            if ws.x_next is None:
+                ws.x_next = tuple(torch.empty_like(t) for t in (ws.x, ws.x_t, ws.x_colpart))
+            ops.adam_step_prep(*enc, coef, lr, beta1, beta2, eps, step,
+                               ops.prep_job(next_batch[0], next_batch[1], ws.x_next[0], ws.x_next[2], ws.x_next[1]))
+        else:
+            step_(*enc, clip_out=ws.clip_out)
+    ws.prep_token = ride
     if not DEC_ADAM_BESIDE_G1 and ws.W_dec_t is None and ws.norm_part is not None:
         # serial: the decoder half (+ the next step's norm partials) on this stream, the whole chip
         dec = [A.dec_part() for A in (P, G, M, V)]
@@ -876,12 +928,16 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
             K, nblk = ws.K, ws.K // 64
             hs = min(ws.h, int(ws.h * DEC_SIDE_ROWS) // 8 * 8)
             dec = [A.dec_part() for A in (P, G, M, V)]
+            # (every row on the side stream: b_dec, the decoder half's trailing elements, goes along -- no norm
+            # partials for them)
+            side_bias = BDEC_IN_SIDE_ADAM and hs == ws.h
+            side_part = dec if side_bias else [t[:hs * K] for t in dec]
             kw = dict(coef=coef if clip_sums is None else None, clip_sums=clip_sums, emulate=emulate)
             hp = (lr, beta1, beta2, eps, step)
             target = None
             if hs > 0:
                 with _span("adam_dec"):
-                    nb = ops.adam_dec_norms(*(t[:hs * K] for t in dec), hs, K, *hp, ws.norm_part[:hs * nblk],
+                    nb = ops.adam_dec_norms(*side_part, hs, K, *hp, ws.norm_part[:hs * nblk],
                                             max_blocks=DEC_ADAM_BLOCKS, done_ctr=ws.adam_done, **kw)
                 ws.adam_done_target = (ws.adam_done_target + nb) & 0xFFFFFFFF
                 target = ws.adam_done_target
@@ -894,12 +950,13 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
                 # kernel_wait (the reader is that G2 launch): G2 waits for the side stream's rows in its kernel
                 # (returns the done counter and its target; P.pending keeps the event for other streams' readers)
                 cur = torch.cuda.current_stream(dev)
-                with _span("adam_dec_rest"):
-                    if ws.h > hs:
-                        ops.adam_dec_norms(*(t[hs * K:] for t in dec), ws.h - hs, K, *hp, ws.norm_part[hs * nblk:],
-                                           **kw)
-                    else:  # (every row on the side stream: b_dec only)
-                        step_(*(t[hs * K:] for t in dec))
+                if not side_bias:
+                    with _span("adam_dec_rest"):
+                        if ws.h > hs:
+                            ops.adam_dec_norms(*(t[hs * K:] for t in dec), ws.h - hs, K, *hp, ws.norm_part[hs * nblk:],
+                                               **kw)
+                        else:  # (every row on the side stream: b_dec only)
+                            step_(*(t[hs * K:] for t in dec))
                 ws.norms_fin_pending = True
                 if kernel_wait and target is not None:
                     P.pending = done

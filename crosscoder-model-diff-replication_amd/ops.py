@@ -527,6 +527,36 @@ def adam_step(p, g, m, v, coef, lr, beta1, beta2, eps, step, max_blocks=0):
                              int(step), int(max_blocks), dtype_code(p.dtype), _stream(p)))
 
 
+def prep_job_ok(x_in, factor, dtype, out_t):
+    """Whether prep_input(x_in, factor, dtype, out_t=out_t) can ride in an Adam launch (prep_job)."""
+    return (out_t is not None and dtype == torch.bfloat16 and x_in.dim() == 3 and x_in.shape[0] % 8 == 0
+            and x_in.shape[2] % 8 == 0 and x_in.dtype in _DT and x_in.is_contiguous() and x_in.data_ptr() % 16 == 0
+            and (factor is None or factor.dtype in _DT))
+
+
+def prep_job(x_in, factor, out, colsum_part, out_t):
+    """prep_input(x_in, factor, bf16, out=out, colsum_part=colsum_part, out_t=out_t) as a job an Adam launch carries
+    (cc_prep_job, adam_step_prep), passed by reference."""
+    B, n, d = x_in.shape
+    _contig(x_in, "x")
+    if out.shape != (B, n * d) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+        raise ValueError("out must be a contiguous bf16 [B, n*d] tensor")
+    if out_t.shape != (n * d, B) or out_t.dtype != torch.bfloat16 or not out_t.is_contiguous():
+        raise ValueError("out_t must be a contiguous bf16 [n*d, B] tensor")
+    fdt = dtype_code(factor.dtype) if factor is not None else CC_F32
+    return ctypes.byref(_lib.PrepJob(x_in.data_ptr(), dtype_code(x_in.dtype),
+                                     factor.data_ptr() if factor is not None else None, fdt, out.data_ptr(),
+                                     out_t.data_ptr(), colsum_part.data_ptr() if colsum_part is not None else None,
+                                     B, n, d))
+
+
+def adam_step_prep(p, g, m, v, coef, lr, beta1, beta2, eps, step, prep):
+    """adam_step (one-pass form, bf16, numel % 8 == 0) whose launch also runs the prep_job `prep`: the same bits as
+    the two launches."""
+    check(lib().cc_adam_step_prep(_ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), _ptr(coef), lr, beta1, beta2, eps,
+                                  int(step), dtype_code(p.dtype), prep, _stream(p)))
+
+
 def adam_step_clip(p, g, m, v, sums, max_norm, emulate_bf16, lr, beta1, beta2, eps, step, max_blocks=0,
                    clip_out=None):
     """adam_step with the clip coefficient formed in the kernel from per-parameter squared sums (fp32 [nparams])."""

@@ -190,6 +190,10 @@ class Trainer:
         cc = self.crosscoder
         raw, factor = self.buffer.next_raw()
         raw = cc.pad_input(raw)  # (zero columns only when d_in % 8 != 0)
+        normalize = getattr(self.buffer, "normalize", True)
+        # the buffer's refresh count tags the batch for engine.PREP_IN_ADAM: the last step's Adam launch may have
+        # prepped exactly these rows
+        tag = getattr(self.buffer, "refresh_count", 0)
         ws = cc._workspace(raw.shape[0], step=True)
         P = cc.arena()
         opt = self.optimizer
@@ -200,7 +204,7 @@ class Trainer:
         # (AuxK: the dead set of this step is the state the last step's dead update left, whose count the host
         # already holds -- none dead: no aux launch is issued and the backward is the plain one)
         aux_on = self.auxk is not None and self._dead_count > 0
-        engine.forward(ws, P, raw, factor if getattr(self.buffer, "normalize", True) else None, finalize=False,
+        engine.forward(ws, P, raw, factor if normalize else None, finalize=False, prep_tag=tag,
                        bt_threshold=(cc.threshold, cc.threshold_beta) if ws.batch_topk is not None else None,
                        aux=(self._since_fired(), self.auxk[2]) if aux_on else None,
                        theta=cc.theta() if ws.jumprelu is not None else None)
@@ -227,8 +231,14 @@ class Trainer:
         g = opt.param_groups[0]
         opt.t += 1
         b1, b2 = g["betas"]
+        # the batch the next step will most likely train on (a buffer that can say, no column padding): its prep
+        # rides in this step's encoder-half Adam launch; a next step handed anything else preps as always
+        peek = getattr(self.buffer, "peek_raw", None) if engine.PREP_IN_ADAM else None
+        nxt = peek() if peek is not None and cc._dp == cc.cfg["d_in"] else None
+        if nxt is not None:
+            nxt = (nxt[0], nxt[1] if normalize else None, getattr(self.buffer, "refresh_count", 0))
         engine.clip_and_adam(ws, P, opt.grads, opt.exp_avg, opt.exp_avg_sq, g["lr"], b1, b2, g["eps"], opt.t,
-                             side_stream=side,
+                             side_stream=side, next_batch=nxt,
                              extra=(ws.theta, opt.theta_grad, opt.theta_m, opt.theta_v) if l0c is not None else None)
         self.scheduler.step()
         self._last_l1c = l1c

@@ -400,6 +400,28 @@ int cc_segment_sums(const float* sq, const int64_t* off, int nparams, int zero_m
 int cc_adam_step(void* p, const void* g, void* m, void* v, int64_t numel, const float* coef, double lr,
                  double beta1, double beta2, double eps, int64_t step, int64_t max_blocks, int dtype, void* stream);
 
+/* A cc_prep_input_t(x_in, in_dtype, factor, factor_dtype, x_out, x_t, colsum_part, B, n, d, CC_BF16) that an Adam
+ * launch carries in its first workgroups (cc_adam_step_prep): the NEXT batch's x, x^T and column-sum partials,
+ * which depend on nothing the step computes.  x_t is required; the same bits as the launch of its own. */
+typedef struct cc_prep_job {
+  const void* x_in;
+  int in_dtype;
+  const void* factor; /* NULL: 1 */
+  int factor_dtype;
+  void* x_out;
+  void* x_t;
+  float* colsum_part; /* optional */
+  int64_t B, n, d;
+} cc_prep_job;
+
+/* cc_adam_step(..., max_blocks = 0, ...) in its one-pass form whose launch also runs `prep` (NULL: cc_adam_step
+ * itself): bf16, numel % 8 == 0.  The same bits as cc_adam_step followed by cc_prep_input_t, one launch fewer:
+ * the step's encoder-half Adam carries the next step's prep.  coef[0] < 0 (CC_CLIP_ABORTED): no update; the
+ * prep still runs. */
+int cc_adam_step_prep(void* p, const void* g, void* m, void* v, int64_t numel, const float* coef, double lr,
+                      double beta1, double beta2, double eps, int64_t step, int dtype, const cc_prep_job* prep,
+                      void* stream);
+
 /* cc_adam_step with clip_grad_norm_'s coefficient formed in the kernel from the per-parameter squared
  * gradient sums `sums` [nparams] (trainer.py:46 over parameters whose sums were combined elsewhere, e.g.
  * all-reduced over the latent shards): the arithmetic of cc_clip_finalize over one element per parameter.

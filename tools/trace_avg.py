@@ -1,6 +1,7 @@
 """Steady-state per-step averages from a rocprofv3 kernel trace of bench.py: for the last N steps (prep kernel to
 prep kernel; the timed steps) the mean step span, each kernel's mean start / end offset and duration in the step
-(by launch position), and the compute stream's idle time.  Usage: python tools/trace_avg.py TRACE.csv [N]"""
+(by launch position), and the compute stream's idle time.  (Where the encoder-half Adam launch carries the prep,
+adam_bulk_prep_kernel, that launch is the boundary: the same step, cut one launch earlier.)  Usage: python tools/trace_avg.py TRACE.csv [N]"""
 import csv
 import statistics
 import sys
