@@ -39,7 +39,8 @@ constexpr int BM = 256, NTHR = 512;
 constexpr uint32_t OOB = 0x7ffffff0u;  // voffset that the range check always rejects
 constexpr uint32_t MAX_RECORDS = 0x7fffffe0u;
 
-enum Epi { EPI_F32 = 0, EPI_ENC = 1, EPI_DEC = 2, EPI_DACTS = 3, EPI_WGDEC = 4, EPI_WGENC = 5, EPI_SPLIT = 6, EPI_DLOSS = 7 };
+enum Epi { EPI_F32 = 0, EPI_ENC = 1, EPI_DEC = 2, EPI_DACTS = 3, EPI_WGDEC = 4, EPI_WGENC = 5, EPI_SPLIT = 6, EPI_DLOSS = 7,
+           EPI_LSCALE = 8 };
 
 struct GemmArgs {
   const void* A;
@@ -52,11 +53,12 @@ struct GemmArgs {
   float* out_f32;       // EPI_DEC fp32 output
   const void* bias;     // b_enc / b_dec, indexed by column
   const float* tn;      // per-column total decoder norm
-  const void* mask_src; // acts (EPI_DACTS), indexed like out
+  const void* mask_src; // acts (EPI_DACTS, EPI_LSCALE), indexed like out
   const void* w_src;    // W_dec (EPI_WGDEC), indexed like out
   const float* norms;   // [h][n] inverse decoder norms (0 where the norm is 0)
   const float* colsum;  // [h] sum_b acts
   float* col_part;      // [nbm * WARPS_M][N]
+  float* col_part2;     // EPI_LSCALE: the column sums of acts^2, like col_part (NULL: not wanted)
   float* wave_part0;    // [nbm*nbn*8]
   float* wave_part1;
   float scale0;
@@ -1380,6 +1382,32 @@ int cc_dacts_bwd(const void* g_recon, const void* W_dec, const void* acts, const
   int rc = check_gemm(a, dtype, true, true);
   if (rc) return rc;
   return launch_dt<EPI_DACTS, true, true>(dtype, a, (hipStream_t)stream);
+}
+
+// Latent scaling's accumulators: the d_acts GEMM's operand geometry (A = Y [B][d], B = W [h][d], both contraction-
+// contiguous; one model's slice of a [.., n*d] matrix is its pointer + m*d with ld = n*d) under the EPI_LSCALE
+// epilogue, always on the general kernel (ragged M / N / K tails, both dtypes).
+int cc_latent_scaling(const void* Y, int64_t ldy, const void* W, int64_t ldw, const void* acts, int64_t lda,
+                      float* dot_part, float* sq_part, int64_t B, int64_t d, int64_t h, int dtype, void* stream) {
+  if (!Y || !W || !acts || !dot_part) return CC_ERR_NULL;
+  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
+  if (B <= 0 || d <= 0 || h <= 0) return CC_ERR_SHAPE;
+  if (d % 8 || h % 4) return CC_ERR_SHAPE;
+  if (ldy < d || ldw < d || lda < h) return CC_ERR_SHAPE;
+  const int64_t es = dtype == CC_BF16 ? 2 : 4;
+  if ((ldy * es) % 16 || (ldw * es) % 16 || (lda * es) % 16) return CC_ERR_ALIGN;
+  if (!al16(Y) || !al16(W) || !al16(acts) || !al16(dot_part) || !al16(sq_part)) return CC_ERR_ALIGN;
+  // (int shapes; a tile's 256 operand / acts rows within one 32-bit buffer offset)
+  if (B > INT32_MAX || d > INT32_MAX || h > INT32_MAX) return CC_ERR_TOO_LARGE;
+  if ((uint64_t)BM * ldy * es >= MAX_RECORDS || (uint64_t)BM * ldw * es >= MAX_RECORDS ||
+      (uint64_t)BM * lda * es >= MAX_RECORDS)
+    return CC_ERR_TOO_LARGE;
+  GemmArgs a = {};
+  a.A = Y; a.lda = ldy; a.B = W; a.ldb = ldw;
+  a.M = (int)B; a.N = (int)h; a.K = (int)d;
+  a.ldo = lda; a.mask_src = acts; a.col_part = dot_part; a.col_part2 = sq_part;
+  if (dtype == CC_BF16) return launch<CC_BF16, true, true, EPI_LSCALE, 256>(a, (hipStream_t)stream);
+  return launch<CC_F32, true, true, EPI_LSCALE, 256>(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

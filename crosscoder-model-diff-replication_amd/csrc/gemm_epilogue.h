@@ -73,7 +73,8 @@ struct FragGeom {
   }
 };
 
-// HBM IO policy: input = mask_src (DACTS) / w_src (WGDEC), output = out, both indexed like out.
+// HBM IO policy: input = mask_src (DACTS, LSCALE) / w_src (WGDEC), output = out, both indexed like out (LSCALE
+// has no out: ldo is the acts pitch).
 template <int DT, int BNT>
 struct RegIO {
   const FragGeom<BNT>& fg;
@@ -408,6 +409,47 @@ CC_DEV void dloss_core(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>::T
   }
 }
 
+// EPI_LSCALE (latent scaling, cc_latent_scaling): the column sums of acts * acc, and optionally of acts^2, per wave
+// row block -- the [M][N] product itself is never stored.  io.in4 = the acts tile, read as EPI_DACTS reads its mask
+// tile; a fragment past the matrix edge loads 0 (and its accumulator is 0: zero-filled operands), so it adds
+// nothing and no range select is needed.  One lane sums its TM rows in ascending order, row16_sum adds the 16 lanes
+// that share the 4 columns: a fixed order, the slab rows of the other epilogues' col_part.
+template <int DT, int BNT, class IO>
+CC_DEV void lscale_core(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>::TM][WaveGeom<BNT>::TN],
+                        const FragGeom<BNT>& fg, const IO& io, int tm, int n0, int wr, int lane) {
+  using WG = WaveGeom<BNT>;
+  constexpr int JB = EPB<DT, BNT>::JB_M;
+  typename V4<DT>::T araw[WG::TM][JB];
+#pragma unroll
+  for (int j = 0; j < WG::TN; ++j) {
+    if (j % JB == 0) {  // the acts vectors of JB column groups, all in flight together
+#pragma unroll
+      for (int jj = 0; jj < JB; ++jj)
+#pragma unroll
+        for (int i = 0; i < WG::TM; ++i) araw[i][jj] = io.in4(i, j + jj);
+    }
+    float dsum[4] = {0.f, 0.f, 0.f, 0.f}, qsum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < WG::TM; ++i) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float f = V4<DT>::get(araw[i][j % JB], e);
+        dsum[e] = __builtin_fmaf(f, acc[i][j][e], dsum[e]);
+        qsum[e] = __builtin_fmaf(f, f, qsum[e]);
+      }
+    }
+    const int64_t at = (int64_t)(tm * WG::WARPS_M + wr) * args.N + n0 + fg.c0 + 16 * j;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) dsum[e] = row16_sum(dsum[e]);
+    if ((lane & 15) == 0 && fg.cv[j]) st4<CC_F32>(args.col_part, at, dsum);
+    if (args.col_part2) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) qsum[e] = row16_sum(qsum[e]);
+      if ((lane & 15) == 0 && fg.cv[j]) st4<CC_F32>(args.col_part2, at, qsum);
+    }
+  }
+}
+
 // cols: EpiCols loaded by the caller (EPI_ENC / EPI_DACTS; otherwise unread).
 // cw: dW_dec L1-term factors loaded by the caller (wgdec_factors; EPI_WGDEC with l1_scale != 0
 // only, otherwise unread).  Passed by reference so they stay in registers.
@@ -428,6 +470,8 @@ CC_DEV float epilogue_core(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT
       enc_fast_core<BNT>(args, acc, fg, io, tm, n0, wr, lane, wave_slot, cols);
     else
       enc_dacts_core<DT, EPI, BNT, FAST && DT == CC_BF16>(args, acc, fg, io, tm, n0, wr, lane, wave_slot, cols);
+  } else if constexpr (EPI == EPI_LSCALE) {
+    lscale_core<DT, BNT>(args, acc, fg, io, tm, n0, wr, lane);
   } else if constexpr (EPI == EPI_DLOSS) {
     static_assert(DT == CC_BF16, "the fused decode + loss epilogue is bf16 only");
     dloss_core<BNT, FAST>(args, acc, fg, io, tm, m0, n0, wr, lane, cols);
@@ -521,7 +565,7 @@ CC_DEV void gemm_epilogue(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>
       }
     }
   } else {
-    const void* in = EPI == EPI_DACTS ? args.mask_src : (EPI == EPI_WGDEC ? args.w_src : nullptr);
+    const void* in = EPI == EPI_DACTS || EPI == EPI_LSCALE ? args.mask_src : (EPI == EPI_WGDEC ? args.w_src : nullptr);
     const RegIO<DT, BNT> io(args, fg, in, m0, n0);
     float cw[WG::TM][WG::TN];
     if constexpr (EPI == EPI_WGDEC) {

@@ -634,6 +634,33 @@ def latent_stats_update(acts, h, k, count, sum_, hist, topk_val, topk_row, row_i
                                        _stream(acts)))
 
 
+# ---------------------------------------------------------------- latent scaling (latent_scaling.py)
+def _pitched(t, cols, name):
+    """(pointer, row pitch) of a 2-D operand with contiguous rows of at least `cols` elements; a column slice
+    of a wider matrix (one model of [.., n*d]) keeps the wide matrix's pitch."""
+    if t.dim() != 2 or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{name} must be [rows, >= {cols}] with contiguous rows, got {tuple(t.shape)}")
+    return _ptr(t), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def latent_scaling(Y, W, acts, dot_part, sq_part=None):
+    """dot_part [col_part_rows(B), h] fp32 <- per 128-row group, sum_i acts[i, j] * (W[j] . Y[i]); sq_part (same
+    shape, optional) <- sum_i acts[i, j]^2 (cc_latent_scaling; reduce_rows over the slab rows gives the sums).
+    Y [B, d], W [h, d] and acts [B, >= h] may be column slices of wider matrices (their row pitch is kept)."""
+    B, d = Y.shape
+    h = W.shape[0]
+    if W.shape[1] != d or acts.shape[0] != B or Y.dtype != W.dtype or Y.dtype != acts.dtype:
+        raise ValueError("latent_scaling: Y [B, d], W [h, d], acts [B, >= h] of one dtype")
+    R = col_part_rows(B)
+    for name, t in (("dot_part", dot_part), ("sq_part", sq_part)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (R, h) or not t.is_contiguous()
+                              or t.device != Y.device):
+            raise ValueError(f"{name} must be a contiguous fp32 tensor of shape ({R}, {h}) on {Y.device}")
+    (py, ldy), (pw, ldw), (pa, lda) = _pitched(Y, d, "Y"), _pitched(W, d, "W"), _pitched(acts, h, "acts")
+    check(lib().cc_latent_scaling(py, ldy, pw, ldw, pa, lda, _ptr(dot_part), _ptr(sq_part), B, d, h,
+                                  dtype_code(Y.dtype), _stream(Y)))
+
+
 # ---------------------------------------------------------------- per-row top-k (TopK crosscoders)
 def topk_part_rows(B, h):
     return int(lib().cc_topk_part_rows(B, h))

@@ -512,6 +512,20 @@ int cc_latent_stats_update(const void* acts, int64_t ld, int64_t B, int64_t h, i
                            int64_t row0, int k, int64_t* count, float* sum, int64_t* hist, float* topk_val,
                            int64_t* topk_row, void* stream);
 
+/* Latent scaling's accumulators (crosscoder_amd.LatentScaling): per latent j, over the batch rows i,
+ *   dot[j] = sum_i acts[i][j] * (W[j][:] . Y[i][:])   and, optionally,   sq[j] = sum_i acts[i][j]^2
+ * as one GEMM whose [B][h] product is never stored: the epilogue multiplies the fp32 accumulator by the acts tile
+ * and writes only its column sums per 128-row group.
+ *   Y [B][ldy], W [h][ldw]: the contraction index d contiguous (the operand geometry of cc_dacts_bwd); one model's
+ *     slice of a [.., n*d] matrix is passed as pointer + m*d with ld = n*d.   acts [B][lda], lda >= h.
+ *   dot_part [cc_col_part_rows(B)][h] (fp32, dense), sq_part the same shape or NULL: cc_reduce_rows over their
+ *     cc_col_part_rows(B) rows gives dot / sq.  Nothing else is written.
+ * Any B >= 1; d % 8 == 0, h % 4 == 0, ldy >= d, ldw >= d, lda >= h (else CC_ERR_SHAPE); every operand pointer and
+ * row pitch (ld * element size) 16-byte aligned (else CC_ERR_ALIGN); 256 rows of an operand within 2 GiB (else
+ * CC_ERR_TOO_LARGE).  No float atomics: the same inputs give the same bits. */
+int cc_latent_scaling(const void* Y, int64_t ldy, const void* W, int64_t ldw, const void* acts, int64_t lda,
+                      float* dot_part, float* sq_part, int64_t B, int64_t d, int64_t h, int dtype, void* stream);
+
 /* Per-row top-k of the activations (TopK crosscoders), one pass over acts [B][ld], first h columns
  * (1 <= k <= h <= 2^17, h % 8 == 0, ld % 8 == 0, ld >= h; acts 16-byte aligned).
  * An element is eligible iff it is > 0: sign clear, not zero, not NaN; +inf and subnormals are eligible, so the
