@@ -11,5 +11,6 @@ from .buffer import Buffer, SyntheticBuffer  # noqa: F401
 from .analysis import decoder_stats, fold_activation_scaling_factor, sae_vis_export  # noqa: F401
 from .latent_stats import LatentStats  # noqa: F401
 from .latent_scaling import LatentScaling  # noqa: F401
+from .decoder_match import match_decoders  # noqa: F401
 
 __version__ = "0.1.0"

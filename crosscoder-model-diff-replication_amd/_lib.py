@@ -126,6 +126,8 @@ SIGNATURES = {
     "cc_latent_stats_max_k": (_i, []),
     "cc_latent_stats_update": (_i, [_p, _i64, _i64, _i64, _i, _p, _i64, _i, _p, _p, _p, _p, _p, _p]),
     "cc_latent_scaling": (_i, [_p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _p]),
+    "cc_decoder_match": (_i, [_p, _i64, _p, _i64, _p, _p, _p, _i64, _i64, _i64, _i64, _i, _i, _p]),
+    "cc_match_reduce": (_i, [_p, _i64, _i64, _p, _p]),
     "cc_topk_part_rows": (_i64, [_i64, _i64]),
     "cc_topk_l0_parts": (_i64, [_i64, _i64]),
     "cc_topk_rows": (_i, [_p, _i64, _i64, _i64, _i, _i, _p, _p, _p, _p, _p, _p]),

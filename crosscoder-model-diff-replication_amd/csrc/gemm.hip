@@ -40,7 +40,7 @@ constexpr uint32_t OOB = 0x7ffffff0u;  // voffset that the range check always re
 constexpr uint32_t MAX_RECORDS = 0x7fffffe0u;
 
 enum Epi { EPI_F32 = 0, EPI_ENC = 1, EPI_DEC = 2, EPI_DACTS = 3, EPI_WGDEC = 4, EPI_WGENC = 5, EPI_SPLIT = 6, EPI_DLOSS = 7,
-           EPI_LSCALE = 8 };
+           EPI_LSCALE = 8, EPI_MATCH = 9 };
 
 struct GemmArgs {
   const void* A;
@@ -83,6 +83,10 @@ struct GemmArgs {
   int pre_blocks;
   LossTailArgs tail;    // the forward's loss tail the launch runs before its tiles (cc_loss_tail_job), tail_items > 0
   int tail_items;
+  // EPI_MATCH (cc_decoder_match): tn = q_scale (per column), flag = exclude_diag, and
+  const float* c_scale; // inverse norm per candidate row, indexed by the row within the launch (row 0 = candidate row0)
+  uint64_t* key_part;   // [nbm * WARPS_M][N] best (score, candidate) keys per wave row block
+  uint32_t row0;        // global candidate index of row 0
 };
 
 typedef __attribute__((address_space(3))) void lds_void;
@@ -1408,6 +1412,33 @@ int cc_latent_scaling(const void* Y, int64_t ldy, const void* W, int64_t ldw, co
   a.ldo = lda; a.mask_src = acts; a.col_part = dot_part; a.col_part2 = sq_part;
   if (dtype == CC_BF16) return launch<CC_BF16, true, true, EPI_LSCALE, 256>(a, (hipStream_t)stream);
   return launch<CC_F32, true, true, EPI_LSCALE, 256>(a, (hipStream_t)stream);
+}
+
+// Decoder matching's fused GEMM: cc_latent_scaling's operand geometry (A = candidates Wc [M][K], B = queries
+// Wq [N][K], both contraction-contiguous) under the EPI_MATCH epilogue, always on the general kernel (ragged M / N /
+// K tails, both dtypes).
+int cc_decoder_match(const void* Wc, int64_t ldc, const void* Wq, int64_t ldq, const float* c_scale,
+                     const float* q_scale, uint64_t* key_part, int64_t M, int64_t N, int64_t K, int64_t row0,
+                     int exclude_diag, int dtype, void* stream) {
+  if (!Wc || !Wq || !c_scale || !q_scale || !key_part) return CC_ERR_NULL;
+  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
+  if (M <= 0 || N <= 0 || K <= 0 || row0 < 0) return CC_ERR_SHAPE;
+  if (K % 8 || N % 4) return CC_ERR_SHAPE;
+  if (ldc < K || ldq < K) return CC_ERR_SHAPE;
+  const int64_t es = dtype == CC_BF16 ? 2 : 4;
+  if ((ldc * es) % 16 || (ldq * es) % 16) return CC_ERR_ALIGN;
+  if (!al16(Wc) || !al16(Wq) || !al16(q_scale) || !al16(key_part) || ((uintptr_t)c_scale & 3)) return CC_ERR_ALIGN;
+  // (int shapes; a tile's 256 operand rows within one 32-bit buffer offset; candidate indices are 32-bit key words)
+  if (M > INT32_MAX || N > INT32_MAX || K > INT32_MAX) return CC_ERR_TOO_LARGE;
+  if (row0 + M > (int64_t)UINT32_MAX) return CC_ERR_TOO_LARGE;
+  if ((uint64_t)BM * ldc * es >= MAX_RECORDS || (uint64_t)BM * ldq * es >= MAX_RECORDS) return CC_ERR_TOO_LARGE;
+  GemmArgs a = {};
+  a.A = Wc; a.lda = ldc; a.B = Wq; a.ldb = ldq;
+  a.M = (int)M; a.N = (int)N; a.K = (int)K;
+  a.ldo = N; a.tn = q_scale; a.c_scale = c_scale + row0; a.key_part = key_part; a.row0 = (uint32_t)row0;
+  a.flag = exclude_diag != 0;
+  if (dtype == CC_BF16) return launch<CC_BF16, true, true, EPI_MATCH, 256>(a, (hipStream_t)stream);
+  return launch<CC_F32, true, true, EPI_MATCH, 256>(a, (hipStream_t)stream);
 }
 
 }  // extern "C"

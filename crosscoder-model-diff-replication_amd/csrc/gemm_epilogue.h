@@ -450,6 +450,78 @@ CC_DEV void lscale_core(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>::
   }
 }
 
+// One butterfly step of row16_max_key: the key of the lane DPP control CTRL pairs this lane with, and the larger
+// of the two as unsigned 64-bit integers.
+template <int CTRL> CC_DEV uint64_t key_max_dpp(uint64_t v) {
+  const uint32_t lo = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)v, CTRL, 0xF, 0xF, false);
+  const uint32_t hi = (uint32_t)__builtin_amdgcn_mov_dpp((int)(uint32_t)(v >> 32), CTRL, 0xF, 0xF, false);
+  const uint64_t o = ((uint64_t)hi << 32) | lo;
+  return o > v ? o : v;
+}
+// unsigned 64-bit max over each aligned group of 16 lanes (every lane gets it): row16_sum's four DPP steps (xor 1,
+// xor 2, row_half_mirror, row_mirror).  A max does not depend on the order.  EXEC must be full.
+CC_DEV uint64_t row16_max_key(uint64_t v) {
+  v = key_max_dpp<0xB1>(v);
+  v = key_max_dpp<0x4E>(v);
+  v = key_max_dpp<0x141>(v);
+  return key_max_dpp<0x140>(v);
+}
+
+// EPI_MATCH (decoder matching, cc_decoder_match): per column (query) j the best (score, candidate) pair over the
+// tile's rows, per wave row block -- the [M][N] similarity matrix is never stored.  The fp32 score of output (i, j) is
+//   s = (acc[i][j] * q_scale[j]) * c_scale[i] + 0.0f      (that multiply order; the add turns -0 into +0)
+// and a pair is one 64-bit key: high word = the score's bits mapped to unsigned order (b ^ 0xffffffff for a set sign
+// bit, b ^ 0x80000000 otherwise), low word = ~(row0 + i).  The unsigned max of the keys is the larger score and, on
+// equal scores, the smaller candidate index; key 0 = no candidate.  Scores are assumed finite (a NaN would order by
+// its bits).  A candidate gives no key if its row lies past M -- unlike EPI_LSCALE, where a zero accumulator adds
+// nothing, its score 0 would beat every negative cosine --, if its c_scale is 0 (a zero row), or if exclude_diag is
+// set and row0 + i == j.  lscale_core's order: one lane walks its TM rows in ascending order (a strict > keeps the
+// smaller index), row16_max_key joins the 16 lanes that share the 4 columns, lane (lane & 15) == 0 stores them to
+// slab row tm * WARPS_M + wr.  Every slab row is written for every column < N (key 0 from a wave with no candidate).
+template <int BNT>
+CC_DEV void match_core(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>::TM][WaveGeom<BNT>::TN],
+                       const FragGeom<BNT>& fg, int tm, int m0, int n0, int wr, int lane) {
+#pragma clang fp contract(off)
+  using WG = WaveGeom<BNT>;
+  const __amdgpu_buffer_rsrc_t rc = vec_rsrc(args.c_scale, m0, args.M, 4);
+  const __amdgpu_buffer_rsrc_t rq = vec_rsrc(args.tn, n0, args.N, 4);
+  float cs[WG::TM];
+  f32x4 qs[WG::TN];
+#pragma unroll
+  for (int i = 0; i < WG::TM; ++i) cs[i] = bldf(rc, fg.rv[i] ? (uint32_t)((fg.r0 + 16 * i) * 4) : OOB);
+#pragma unroll
+  for (int j = 0; j < WG::TN; ++j) qs[j] = bld4<CC_F32>(rq, fg.cv[j] ? (uint32_t)((fg.c0 + 16 * j) * 4) : OOB);
+#pragma unroll
+  for (int j = 0; j < WG::TN; ++j) {
+    const uint32_t col = (uint32_t)(n0 + fg.c0 + 16 * j);
+    uint32_t bh[4] = {0u, 0u, 0u, 0u}, bl[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (int i = 0; i < WG::TM; ++i) {
+      const uint32_t gi = args.row0 + (uint32_t)(m0 + fg.r0 + 16 * i);
+      const bool row_ok = fg.rv[i] && cs[i] != 0.f;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float s = (acc[i][j][e] * qs[j][e]) * cs[i] + 0.0f;
+        const uint32_t b = __float_as_uint(s);
+        const uint32_t h = b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u);
+        const bool ok = row_ok && !(args.flag && gi == col + (uint32_t)e);
+        if (ok && h > bh[e]) {
+          bh[e] = h;
+          bl[e] = ~gi;
+        }
+      }
+    }
+    uint64_t key[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) key[e] = row16_max_key(((uint64_t)bh[e] << 32) | bl[e]);
+    if ((lane & 15) == 0 && fg.cv[j]) {
+      u32x4* p = (u32x4*)(args.key_part + (int64_t)(tm * WG::WARPS_M + wr) * args.N + col);
+      p[0] = u32x4{(uint32_t)key[0], (uint32_t)(key[0] >> 32), (uint32_t)key[1], (uint32_t)(key[1] >> 32)};
+      p[1] = u32x4{(uint32_t)key[2], (uint32_t)(key[2] >> 32), (uint32_t)key[3], (uint32_t)(key[3] >> 32)};
+    }
+  }
+}
+
 // cols: EpiCols loaded by the caller (EPI_ENC / EPI_DACTS; otherwise unread).
 // cw: dW_dec L1-term factors loaded by the caller (wgdec_factors; EPI_WGDEC with l1_scale != 0
 // only, otherwise unread).  Passed by reference so they stay in registers.
@@ -564,6 +636,8 @@ CC_DEV void gemm_epilogue(const GemmArgs& args, const f32x4 (&acc)[WaveGeom<BNT>
         }
       }
     }
+  } else if constexpr (EPI == EPI_MATCH) {
+    match_core<BNT>(args, acc, fg, tm, m0, n0, wr, lane);
   } else {
     const void* in = EPI == EPI_DACTS || EPI == EPI_LSCALE ? args.mask_src : (EPI == EPI_WGDEC ? args.w_src : nullptr);
     const RegIO<DT, BNT> io(args, fg, in, m0, n0);

@@ -661,6 +661,47 @@ def latent_scaling(Y, W, acts, dot_part, sq_part=None):
                                   dtype_code(Y.dtype), _stream(Y)))
 
 
+# ---------------------------------------------------------------- decoder matching (decoder_match.py)
+def _keys(t, shape, name, dev):
+    if t.dtype != torch.int64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+        raise ValueError(f"{name} must be a contiguous int64 tensor of shape {shape} on {dev}")
+    return _ptr(t)
+
+
+def decoder_match(Wc, Wq, c_scale, q_scale, key_part, row0=0, exclude_diag=False):
+    """key_part [col_part_rows(M), N] int64 <- per 128-row group of the M candidates Wc [M, K] (global indices
+    row0 .. row0 + M - 1) and per query row of Wq [N, K], the best (cosine, candidate) pair as a 64-bit key
+    (cc_decoder_match; match_reduce folds the slab rows into the running best).  c_scale [>= row0 + M] is the whole
+    candidate set's fp32 inverse norms, q_scale [N] the queries'.  Wc and Wq may be row or column slices of wider
+    matrices (their row pitch is kept)."""
+    M, K = Wc.shape
+    N = Wq.shape[0]
+    if Wq.shape[1] != K or Wc.dtype != Wq.dtype or Wc.device != Wq.device:
+        raise ValueError("decoder_match: Wc [M, K] and Wq [N, K] of one dtype on one device")
+    if isinstance(row0, bool) or not isinstance(row0, int) or row0 < 0:
+        raise ValueError(f"row0 must be an int >= 0, got {row0!r}")
+    for name, t, least in (("c_scale", c_scale, row0 + M), ("q_scale", q_scale, N)):
+        if (t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.device != Wc.device
+                or (t.shape[0] < least if name == "c_scale" else t.shape[0] != least)):
+            raise ValueError(f"{name} must be a contiguous fp32 vector of {'at least ' if name == 'c_scale' else ''}"
+                             f"{least} elements on {Wc.device}")
+    pk = _keys(key_part, (col_part_rows(M), N), "key_part", Wc.device)
+    (pc, ldc), (pq, ldq) = _pitched(Wc, K, "Wc"), _pitched(Wq, K, "Wq")
+    check(lib().cc_decoder_match(pc, ldc, pq, ldq, _ptr(c_scale), _ptr(q_scale), pk, M, N, K, row0,
+                                 1 if exclude_diag else 0, dtype_code(Wc.dtype), _stream(Wc)))
+
+
+def match_reduce(key_part, best):
+    """best [N] int64 (in/out; zeros = nothing seen) <- max(best, max over the rows of key_part [R, N]) as unsigned
+    64-bit keys (cc_match_reduce)."""
+    if key_part.dim() != 2 or key_part.shape[0] < 1:
+        raise ValueError(f"key_part must be [R >= 1, N], got {tuple(key_part.shape)}")
+    R, N = key_part.shape
+    pk = _keys(key_part, (R, N), "key_part", key_part.device)
+    pb = _keys(best, (N,), "best", key_part.device)
+    check(lib().cc_match_reduce(pk, R, N, pb, _stream(key_part)))
+
+
 # ---------------------------------------------------------------- per-row top-k (TopK crosscoders)
 def topk_part_rows(B, h):
     return int(lib().cc_topk_part_rows(B, h))

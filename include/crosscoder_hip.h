@@ -526,6 +526,30 @@ int cc_latent_stats_update(const void* acts, int64_t ld, int64_t B, int64_t h, i
 int cc_latent_scaling(const void* Y, int64_t ldy, const void* W, int64_t ldw, const void* acts, int64_t lda,
                       float* dot_part, float* sq_part, int64_t B, int64_t d, int64_t h, int dtype, void* stream);
 
+/* Decoder matching (crosscoder_amd.match_decoders): for every query row j of Wq, the candidate row of Wc with the
+ * largest cosine, as one GEMM whose [M][N] similarity matrix is never stored.  Per output (i, j) the epilogue forms
+ *   s = (acc[i][j] * q_scale[j]) * c_scale[row0 + i] + 0.0f        (fp32, that order; -0 becomes +0)
+ * and keeps per query and 128-row group the best pair as a 64-bit key: high word = the bits b of s mapped to unsigned
+ * order (b ^ 0xffffffff if the sign bit is set, b ^ 0x80000000 otherwise), low word = ~(row0 + i).  The unsigned max of
+ * two keys is the larger score and, on equal scores, the smaller candidate index; key 0 = no candidate.  Scores are
+ * assumed finite (finite operands and scales); a NaN score would be ordered by its bits.
+ *   Wc [M][ldc]: this launch's M candidates, global indices row0 .. row0 + M - 1;  Wq [N][ldq]: the queries; the
+ *     contraction index K contiguous in both; one model's slice of a [.., n*d] matrix is pointer + m*d with ld = n*d.
+ *   c_scale [>= row0 + M], q_scale [N]: fp32 inverse norms, 0 where the norm is 0.  c_scale is the whole candidate
+ *     set's vector (indexed by the global index), q_scale 16-byte aligned.
+ *   key_part [cc_col_part_rows(M)][N] (dense): every element is written.
+ * A candidate gives no key if c_scale[row0 + i] == 0, or if exclude_diag != 0 and row0 + i == j; rows past M never do.
+ * cc_match_reduce folds a slab into the running state: best[j] = max(best[j], max_r part[r][j]) over R rows, N
+ * columns; best [N] in/out (zero = nothing seen yet).  An integer max: any chunking of the candidates and any slab
+ * row order give the same bits.
+ * Any M >= 1; K % 8 == 0, N % 4 == 0, ldc >= K, ldq >= K, row0 >= 0 (else CC_ERR_SHAPE); Wc, Wq, q_scale, key_part and
+ * the row pitches 16-byte aligned, c_scale 4-byte, part / best 8-byte (else CC_ERR_ALIGN); 256 rows of an operand within
+ * 2 GiB and row0 + M < 2^32 (else CC_ERR_TOO_LARGE). */
+int cc_decoder_match(const void* Wc, int64_t ldc, const void* Wq, int64_t ldq, const float* c_scale,
+                     const float* q_scale, uint64_t* key_part, int64_t M, int64_t N, int64_t K, int64_t row0,
+                     int exclude_diag, int dtype, void* stream);
+int cc_match_reduce(const uint64_t* part, int64_t R, int64_t N, uint64_t* best, void* stream);
+
 /* Per-row top-k of the activations (TopK crosscoders), one pass over acts [B][ld], first h columns
  * (1 <= k <= h <= 2^17, h % 8 == 0, ld % 8 == 0, ld >= h; acts 16-byte aligned).
  * An element is eligible iff it is > 0: sign clear, not zero, not NaN; +inf and subnormals are eligible, so the
