@@ -137,6 +137,7 @@ SIGNATURES = {
     "cc_batch_topk": (_i, [_p, _i64, _i64, _i64, _i, _p, _i64, _p, _p, _p, _p, _p, _p, _f, _p, _i64, _p]),
     "cc_threshold_mask": (_i, [_p, _i64, _i64, _i64, _i, _p, _p, _p, _p, _p, _p, _p]),
     "cc_adam_step": (_i, [_p, _p, _p, _p, _i64, _p, _d, _d, _d, _d, _i64, _i64, _i, _p]),
+    "cc_adam_master_step": (_i, [_p, _p, _p, _p, _p, _i64, _p, _d, _d, _d, _d, _i64, _i64, _p]),
     "cc_adam_step_prep": (_i, [_p, _p, _p, _p, _i64, _p, _d, _d, _d, _d, _i64, _i, _p, _p]),
     "cc_adam_step_clip": (_i, [_p, _p, _p, _p, _i64, _p, _i, _f, _i, _p, _d, _d, _d, _d, _i64, _i64, _i, _p]),
     "cc_adam_dec_norms": (_i, [_p, _p, _p, _p, _i64, _p, _p, _i, _f, _i, _d, _d, _d, _d, _i64, _i64, _p, _i64, _i64, _i,

@@ -153,6 +153,17 @@ def auxk_options(cfg, n_models=2):
     return float(coeff), k_aux, dead
 
 
+def master_weights_of(cfg):
+    """cfg["master_weights"] (framework extension; the key travels in the checkpoint's cfg json): a bool, absent or
+    False: off.  True on a bf16 crosscoder: Trainer keeps fp32 master weights and fp32 Adam moments, and the bf16
+    parameters are the masters rounded after every update.  On an fp32 crosscoder it changes
+    nothing: the parameters are their own masters."""
+    mw = cfg.get("master_weights", False)
+    if not isinstance(mw, bool):
+        raise ValueError(f"cfg['master_weights'] must be a bool, got {mw!r}")
+    return mw
+
+
 class CrossCoder(nn.Module):
     def __init__(self, cfg, n_models: Optional[int] = None, init_W_dec: Optional[torch.Tensor] = None):
         """init_W_dec (framework extension): start from this decoder ([h, n, d], W_enc = its rearranged
@@ -165,6 +176,7 @@ class CrossCoder(nn.Module):
         d_in = cfg["d_in"]
         self.n_models = int(n_models if n_models is not None else cfg.get("n_models", 2))
         self.auxk = auxk_options(cfg, self.n_models)  # (auxk_coeff, k_aux, dead_tokens) or None: Trainer.step's
+        master_weights_of(cfg)  # (validated here; Trainer's optimizer is what it switches)
         self.dtype = DTYPES[cfg["enc_dtype"]]
         if self.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("crosscoder_amd kernels support enc_dtype 'bf16' and 'fp32'")

@@ -954,6 +954,66 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void a
   if (a.done_ctr) adam_signal_done(a.done_ctr);
 }
 
+// The master-weight Adam (cc_adam_master_step): a bf16 crosscoder trained with fp32 masters and fp32 moments.
+// adam_elem<CC_F32> on g = float(g16) over p32 / m32 / v32 -- the bits of the fp32 cc_adam_step -- then p16 = p32
+// rounded (f2bf) into the bf16 arena the GEMMs read.  8 elements per thread: 16 B of g16, 2 x 16 B each of p32 /
+// m32 / v32, one 16-byte store of p16.  g / m / v / p32 are touched once per step: non-temporal, as
+// adam_bulk_kernel streams them; p16 stays temporal, G1 / G2 read it next.  No LDS (the capped form runs beside
+// G1, see adam_kernel).
+CC_DEV void adam_master_load(const AdamArgs& a, int64_t i, float p[8], bf16x8& g, float m[8], float v[8]) {
+  load8_nt<CC_F32>(a.p, i, p);
+  g = __builtin_nontemporal_load((const bf16x8*)((const bf16_t*)a.g + i));
+  load8_nt<CC_F32>(a.m, i, m);
+  load8_nt<CC_F32>(a.v, i, v);
+}
+CC_DEV void adam_master_chunk(const AdamArgs& a, float coef, int64_t i, float p[8], const bf16x8& g, float m[8],
+                              float v[8], bf16_t* p16) {
+  bf16x8 r;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    adam_elem<CC_F32>(a, coef, p[j], bf2f((bf16_t)g[j]), m[j], v[j]);
+    r[j] = (short)f2bf(p[j]);
+  }
+  store8_nt<CC_F32>(a.p, i, p);
+  store8_nt<CC_F32>(a.m, i, m);
+  store8_nt<CC_F32>(a.v, i, v);
+  *(bf16x8*)(p16 + i) = r;
+}
+// STRIDE: the capped grid-stride form (the side stream's); false: one chunk per thread, its loads issued before
+// the coefficient arrives (as adam_bulk_kernel).  The last numel % 8 elements: one thread each of block 0.
+// coef < 0 (CC_CLIP_ABORTED): nothing is stored.
+template <bool STRIDE>
+__global__ __launch_bounds__(256) void adam_master_kernel(const AdamArgs a, bf16_t* __restrict__ p16) {
+  const int64_t nfull = a.numel & ~(int64_t)7;
+  const int64_t i0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 8;
+  float p[8], m[8], v[8], coef;
+  bf16x8 g;
+  if constexpr (STRIDE) {
+    coef = a.coef ? *a.coef : 1.f;
+    if (coef < 0.f) return;
+    const int64_t stride = (int64_t)gridDim.x * 256 * 8;
+    for (int64_t i = i0; i < nfull; i += stride) {
+      adam_master_load(a, i, p, g, m, v);
+      adam_master_chunk(a, coef, i, p, g, m, v, p16);
+    }
+  } else {
+    const bool in = i0 < nfull;
+    if (in) adam_master_load(a, i0, p, g, m, v);
+    coef = a.coef ? *a.coef : 1.f;
+    if (coef < 0.f) return;
+    if (in) adam_master_chunk(a, coef, i0, p, g, m, v, p16);
+  }
+  const int64_t k = nfull + threadIdx.x;
+  if (blockIdx.x == 0 && k < a.numel) {
+    float pk = ((const float*)a.p)[k], mk = ((const float*)a.m)[k], vk = ((const float*)a.v)[k];
+    adam_elem<CC_F32>(a, coef, pk, bf2f(((const bf16_t*)a.g)[k]), mk, vk);
+    ((float*)a.p)[k] = pk;
+    ((float*)a.m)[k] = mk;
+    ((float*)a.v)[k] = vk;
+    p16[k] = f2bf(pk);
+  }
+}
+
 // Decoder-half Adam over W_dec [h][K] (bf16) in 64 x 64 tiles that also emits what the next
 // step needs from the updated W_dec: W_dec^T [K][h] (LDS tile read back with ds_read_b64_tr_b16)
 // and the decoder norms' per-(row, 64-column block) squared sums in dec_norms_kernel's order
@@ -1444,6 +1504,27 @@ int cc_adam_step_clip(void* p, const void* g, void* m, void* v, int64_t numel, c
   a.clip_max_norm = max_norm;
   a.clip_out = clip_out;
   return adam_launch(a, max_blocks, dtype, (hipStream_t)stream);
+}
+
+int cc_adam_master_step(void* p32, const void* g16, void* m32, void* v32, void* p16, int64_t numel, const float* coef,
+                        double lr, double beta1, double beta2, double eps, int64_t step, int64_t max_blocks,
+                        void* stream) {
+  if (!p32 || !g16 || !m32 || !v32 || !p16) return CC_ERR_NULL;
+  if (numel <= 0 || step <= 0) return CC_ERR_SHAPE;
+  if (!al16(p32) || !al16(g16) || !al16(m32) || !al16(v32) || !al16(p16)) return CC_ERR_ALIGN;
+  const AdamArgs a = adam_args(p32, g16, m32, v32, numel, coef, lr, beta1, beta2, eps, step);
+  hipStream_t st = (hipStream_t)stream;
+  if (max_blocks > 0) {  // capped grid-stride form: leaves most CUs to a concurrent GEMM
+    const int64_t blocks = adam_capped_blocks(numel, max_blocks);
+    if (blocks > INT32_MAX) return CC_ERR_SHAPE;
+    hipLaunchKernelGGL(adam_master_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, st, a, (bf16_t*)p16);
+  } else {
+    const int64_t blocks = ((numel + 7) / 8 + 255) / 256;
+    if (blocks > INT32_MAX) return CC_ERR_SHAPE;
+    hipLaunchKernelGGL(adam_master_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, st, a, (bf16_t*)p16);
+  }
+  CC_LAUNCH_CHECK();
+  return CC_OK;
 }
 
 int cc_adam_step_prep(void* p, const void* g, void* m, void* v, int64_t numel, const float* coef, double lr,

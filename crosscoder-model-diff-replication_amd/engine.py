@@ -843,17 +843,34 @@ SERIAL_DEC_BLOCKS = 0  # (0: the library's default grid for the serial form)
 
 
 def clip_and_adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, max_norm=1.0, side_stream=None, extra=None,
-                  next_batch=None):
+                  next_batch=None, master=None):
     """clip_grad_norm_ (from the squared-sum slabs of the backward) + Adam (see adam())."""
     emulate = clip_emulation(ws, len(ws.sq_off) - 1)
     if not ws.clip_ready:
         ops.clip_finalize(ws.sq, ws.sq_off, max_norm, emulate, ws.clip_out)
     ws.clip_ready = False
-    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream, extra=extra, next_batch=next_batch)
+    adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream, extra=extra, next_batch=next_batch, master=master)
+
+
+def _adam_master(ws, P, G, M, V, master, hp, side_stream, clip_sums):
+    """adam()'s launch with fp32 master weights (cc_adam_master_step): `master`, M and V are fp32 arenas, G the bf16
+    gradients, and P, the bf16 arena the GEMMs read, receives the rounded masters.  One launch over the whole arena
+    on torch's stream, then the next step's decoder norms (/ W_dec^T) from the rounded W_dec on the same stream;
+    nothing is pending afterwards.  The side stream is not used: with the decoder half on it, ordered for its readers
+    by an event as in adam()'s last branch, a snapshot taken after Trainer.synchronize() intermittently held the
+    decoder half from before the update (DESIGN.md sections 3.16 and 3.7; the cause is not found).  No prep ride:
+    the next forward preps."""
+    if clip_sums is not None:
+        raise ValueError("master weights take the step's own coefficient")
+    ws.prep_token = None
+    with _span("adam"):
+        ops.adam_master_step(master.data, G.data, M.data, V.data, P.data, *hp)
+    if side_stream is not None:  # (the Trainer's step: the standalone form leaves the norms to the next forward)
+        norms_for_next(ws, P)
 
 
 def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sums=None, extra=None,
-         next_batch=None):
+         next_batch=None, master=None):
     """Adam with the clip coefficient in ws.clip_out[0] -- or, clip_sums (sums [4], max_norm): formed in each
     launch from the per-parameter squared gradient sums (cc_adam_step_clip; the encoder-half launch also writes
     ws.clip_out), so no clip launch sits between the sums' all-reduce and Adam.  side_stream: the encoder half runs on torch's
@@ -865,7 +882,8 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
     same coefficient and hyper-parameters, on torch's stream before anything else.
     next_batch ((x_in, factor, tag), with a side stream): the raw batch the next forward(ws, ..., prep_tag=tag) will most
     likely be handed, unchanged until then; where the shapes allow, its prep rides in the encoder half's launch
-    (PREP_IN_ADAM) and that forward launches none.  A forward handed anything else runs its prep as always."""
+    (PREP_IN_ADAM) and that forward launches none.  A forward handed anything else runs its prep as always.
+    master (an fp32 Arena, with fp32 M and V; a bf16 P): the master-weight update instead (_adam_master)."""
     P.wait_pending()  # (no deferred rows of an earlier step may read this step's coefficient)
     P.updates += 1
     coef = ws.clip_out[0:1]
@@ -883,6 +901,9 @@ def adam(ws, P, G, M, V, lr, beta1, beta2, eps, step, side_stream=None, clip_sum
             ops.adam_step_clip(p, g, m, v, clip_sums[0], clip_sums[1], emulate, lr, beta1, beta2, eps, step,
                                max_blocks=max_blocks, clip_out=clip_out)
 
+    if master is not None:
+        _adam_master(ws, P, G, M, V, master, (coef, lr, beta1, beta2, eps, step), side_stream, clip_sums)
+        return
     if side_stream is None:
         with _span("adam"):
             step_(P.data, G.data, M.data, V.data, clip_out=ws.clip_out)

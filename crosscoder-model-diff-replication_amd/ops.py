@@ -527,6 +527,20 @@ def adam_step(p, g, m, v, coef, lr, beta1, beta2, eps, step, max_blocks=0):
                              int(step), int(max_blocks), dtype_code(p.dtype), _stream(p)))
 
 
+def adam_master_step(p32, g16, m32, v32, p16, coef, lr, beta1, beta2, eps, step, max_blocks=0):
+    """The master-weight Adam step (cc_adam_master_step): fp32 p32 / m32 / v32 updated in place from the bf16
+    gradient g16 with the bits of the fp32 adam_step on g16.float(), and p16 = p32 rounded to bf16.  All flat,
+    contiguous, of one length and on one device; max_blocks as adam_step's."""
+    n = p32.numel()
+    for name, t, dt in (("p32", p32, torch.float32), ("g16", g16, torch.bfloat16), ("m32", m32, torch.float32),
+                        ("v32", v32, torch.float32), ("p16", p16, torch.bfloat16)):
+        if t.dtype != dt or t.numel() != n or t.device != p32.device:
+            raise ValueError(f"adam_master_step: {name} must be a {dt} tensor of {n} elements on {p32.device}")
+        _contig(t, name)
+    check(lib().cc_adam_master_step(_ptr(p32), _ptr(g16), _ptr(m32), _ptr(v32), _ptr(p16), n, _ptr(coef), lr, beta1,
+                                    beta2, eps, int(step), int(max_blocks), _stream(p32)))
+
+
 def prep_job_ok(x_in, factor, dtype, out_t):
     """Whether prep_input(x_in, factor, dtype, out_t=out_t) can ride in an Adam launch (prep_job)."""
     return (out_t is not None and dtype == torch.bfloat16 and x_in.dim() == 3 and x_in.shape[0] % 8 == 0

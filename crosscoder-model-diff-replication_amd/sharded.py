@@ -294,6 +294,11 @@ class ShardedTrainer:
         if cfg.get("auxk_coeff", 0) or getattr(crosscoder, "auxk", None) is not None:
             raise ValueError("ShardedTrainer does not serve auxk_coeff > 0: the AuxK dead-latent loss belongs to TopK / "
                              "BatchTopK crosscoders, which train with Trainer")
+        crosscoder_cfg = getattr(crosscoder, "cfg", None) or {}
+        if cfg.get("master_weights", False) or crosscoder_cfg.get("master_weights", False):
+            raise ValueError("ShardedTrainer does not serve master_weights: its Adam launches form the clip coefficient "
+                             "from the all-reduced sums (cc_adam_step_clip), which the master-weight update does not "
+                             "take; train with Trainer")
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)

@@ -6,14 +6,16 @@ crosscoder, whose "loss" includes l0_coeff * l0_loss and whose thresholds the st
 sequence of engine.py and reads the 6 loss scalars once, from mapped host memory the loss-tail
 kernel writes directly (the reference does 7 `.item()` syncs).  Adam state (exp_avg / exp_avg_sq, bf16 like the
 reference's) lives in arenas mirroring the parameter arena, exposed through
-`optimizer.state[param]` for inspection.
+`optimizer.state[param]` for inspection.  cfg["master_weights"] = True (bf16 crosscoders) keeps fp32 master weights and
+fp32 moments instead, the bf16 parameters being the masters rounded after every update (DESIGN.md section 3.16);
+`Trainer.state_dict()` / `load_state_dict()` carry the optimizer's state across a restart in either mode.
 """
 import torch
 import tqdm
 
 from . import _hip, engine
 from .buffer import Buffer
-from .crosscoder import CrossCoder
+from .crosscoder import CrossCoder, master_weights_of
 
 
 def reference_loss(l2, l1, l1c, dtype):
@@ -37,12 +39,21 @@ def rounded(v, dtype):
 class FusedAdam:
     """State holder with torch.optim.Adam's observable surface (param_groups, state)."""
 
-    def __init__(self, cc, lr, betas, eps=1e-8):
+    def __init__(self, cc, lr, betas, eps=1e-8, master_weights=False):
+        """master_weights (cfg["master_weights"]) on a bf16 crosscoder: `master`, an fp32 arena of the parameters, and
+        fp32 moments; the bf16 parameters are the masters rounded after every update (cc_adam_master_step).  On an
+        fp32 crosscoder the flag changes nothing."""
         a = cc.arena()
         self.cc = cc
-        self.exp_avg = a.like()
-        self.exp_avg_sq = a.like()
+        self.master_mode = bool(master_weights) and cc.dtype == torch.bfloat16
+        state_dtype = torch.float32 if self.master_mode else None
+        self.exp_avg = a.like(dtype=state_dtype)
+        self.exp_avg_sq = a.like(dtype=state_dtype)
         self.grads = a.like()
+        self.master = None
+        self._master_token = None  # _arena_token of the bf16 arena when it last was the masters rounded
+        if self.master_mode:
+            self.master_for_update()
         # a JumpReLU crosscoder's thresholds: fp32 gradient and moments over the kernel h, in every mode
         self.theta_grad = self.theta_m = self.theta_v = None
         if cc.activation == "jumprelu":
@@ -51,14 +62,49 @@ class FusedAdam:
         self.param_groups = [{"lr": lr, "initial_lr": lr, "betas": betas, "eps": eps, "weight_decay": 0.0}]
         self.t = 0
 
+    @staticmethod
+    def _arena_token(a):
+        # what the bf16 arena is keyed on (as engine._norms_token): its storage, the version counter every view of
+        # it shares (any in-place write through torch bumps it; our Adam kernels do not) and the count of kernel
+        # writes (Arena.updates: Adam's, fold_activation_scaling_factor's)
+        return (a.data.data_ptr(), a.data._version, a.updates)
+
+    def master_for_update(self):
+        """The master arena for the next Adam launch (None outside master mode).  If the bf16 parameters were written
+        since the last update (load_state_dict, fold_activation_scaling_factor, user code), the masters of the
+        elements that no longer round to their parameter are re-seeded from it first; every other master keeps its
+        extra bits, and the moments stay, as torch's would."""
+        if not self.master_mode:
+            return None
+        a = self.cc.arena()
+        tok = self._arena_token(a)
+        if self._master_token != tok:
+            a.wait_pending()  # the decoder half may still be updating on the side stream
+            if (self.master is None or self.master.data.device != a.data.device
+                    or self.master.data.shape != a.data.shape):
+                self.master = a.like(dtype=torch.float32)
+                self.master.data.copy_(a.data)
+            else:
+                keep = self.master.data.to(a.data.dtype) == a.data
+                self.master.data.copy_(torch.where(keep, self.master.data, a.data.float()))
+            self._master_token = tok
+        return self.master
+
+    def master_updated(self):
+        """After the step's Adam launches: the bf16 arena is the masters rounded."""
+        self._master_token = self._arena_token(self.cc.arena())
+
     @property
     def state(self):
         self.cc.arena().wait_pending()  # the decoder half may still be updating on the side stream
         m, v = self.exp_avg.views(), self.exp_avg_sq.views()
+        w = self.master_for_update().views() if self.master_mode else None
         st = {}
         for name in ("W_enc", "W_dec", "b_enc", "b_dec"):
             p = getattr(self.cc, name)
             st[p] = {"step": torch.tensor(float(self.t)), "exp_avg": m[name], "exp_avg_sq": v[name]}
+            if w is not None:
+                st[p]["master"] = w[name]
         if self.theta_m is not None:
             h = self.cc.d_hidden
             st[self.cc.jump_threshold] = {"step": torch.tensor(float(self.t)), "exp_avg": self.theta_m[:h],
@@ -67,6 +113,55 @@ class FusedAdam:
 
     def zero_grad(self, set_to_none=True):
         pass  # grads are overwritten (never accumulated) by the backward kernels
+
+    def state_dict(self):
+        """What a restart needs beside CrossCoder.save(): the step count, both moments as flat arenas in their own
+        dtype, in master mode the master arena, and a JumpReLU crosscoder's threshold moments (clones)."""
+        self.cc.arena().wait_pending()
+        sd = {"step": self.t, "master_weights": self.master_mode,
+              "exp_avg": self.exp_avg.data.detach().clone(), "exp_avg_sq": self.exp_avg_sq.data.detach().clone()}
+        if self.master_mode:
+            sd["master"] = self.master_for_update().data.detach().clone()
+        if self.theta_m is not None:
+            sd["theta_exp_avg"] = self.theta_m.detach().clone()
+            sd["theta_exp_avg_sq"] = self.theta_v.detach().clone()
+        return sd
+
+    def check_state_dict(self, sd):
+        """ValueError unless `sd` is state_dict()'s output of an optimizer of the same mode, shapes and dtypes; writes
+        nothing.  Returns the destination of every tensor entry."""
+        if not isinstance(sd, dict) or not isinstance(sd.get("step"), int) or isinstance(sd.get("step"), bool) \
+                or sd["step"] < 0:
+            raise ValueError("FusedAdam.load_state_dict: not a FusedAdam state dict (no integer 'step' >= 0)")
+        if bool(sd.get("master_weights", False)) != self.master_mode:
+            raise ValueError(f"FusedAdam.load_state_dict: the state was saved with master_weights="
+                             f"{bool(sd.get('master_weights', False))}, this optimizer runs with {self.master_mode}")
+        want = {"exp_avg": self.exp_avg.data, "exp_avg_sq": self.exp_avg_sq.data}
+        if self.master_mode:
+            want["master"] = self.master_for_update().data
+        if self.theta_m is not None:
+            want["theta_exp_avg"], want["theta_exp_avg_sq"] = self.theta_m, self.theta_v
+        extra = set(sd) - set(want) - {"step", "master_weights"}
+        if extra:
+            raise ValueError(f"FusedAdam.load_state_dict: unexpected entries {sorted(extra)}")
+        for k, dst in want.items():
+            t = sd.get(k)
+            if not torch.is_tensor(t) or tuple(t.shape) != tuple(dst.shape) or t.dtype != dst.dtype:
+                got = (tuple(t.shape), t.dtype) if torch.is_tensor(t) else t
+                raise ValueError(f"FusedAdam.load_state_dict: {k!r} must be a {dst.dtype} tensor of shape "
+                                 f"{tuple(dst.shape)}, got {got}")
+        return want
+
+    def load_state_dict(self, sd):
+        """Takes state_dict()'s output of an optimizer of the same mode, shapes and dtypes (ValueError otherwise;
+        nothing is written then).  The masters of parameters that are not their rounding -- the crosscoder was
+        loaded from something else -- are re-seeded from the parameters before the next update."""
+        want = self.check_state_dict(sd)
+        self.cc.arena().wait_pending()
+        for k, dst in want.items():
+            dst.copy_(sd[k])
+        self.t = sd["step"]
+        self._master_token = None  # (checked against the parameters before the next update)
 
 
 class LambdaLRHost:
@@ -104,7 +199,9 @@ class Trainer:
         self.crosscoder = crosscoder if crosscoder is not None else CrossCoder(cfg)
         self.buffer = buffer if buffer is not None else Buffer(cfg, model_A, model_B, all_tokens)
         self.total_steps = cfg["num_tokens"] // cfg["batch_size"]
-        self.optimizer = FusedAdam(self.crosscoder, cfg["lr"], (cfg["beta1"], cfg["beta2"]))
+        # cfg["master_weights"] (bf16 crosscoders): fp32 master weights and fp32 Adam moments, DESIGN.md section 3.16
+        self.optimizer = FusedAdam(self.crosscoder, cfg["lr"], (cfg["beta1"], cfg["beta2"]),
+                                   master_weights=master_weights_of(cfg))
         self.scheduler = LambdaLRHost(self.optimizer, self.lr_lambda)
         self.step_counter = 0
         self.logger = logger
@@ -160,11 +257,20 @@ class Trainer:
     @tokens_since_fired.setter
     def tokens_since_fired(self, value):
         cur = self.tokens_since_fired
-        value = torch.as_tensor(value)
-        if tuple(value.shape) != tuple(cur.shape) or value.dtype.is_floating_point or bool((value < 0).any()):
-            raise ValueError(f"tokens_since_fired takes a non-negative integer tensor of shape {tuple(cur.shape)}")
+        value = self._checked_since_fired(value)
         cur.copy_(value.to(cur.device, torch.int64))
         self._dead_count = int((cur >= self.auxk[2]).sum())
+
+    def _checked_since_fired(self, value):
+        # what the tokens_since_fired setter accepts, as a tensor (ValueError otherwise; nothing is written)
+        if self.auxk is None:
+            raise ValueError("tokens_since_fired: cfg['auxk_coeff'] is 0 or absent")
+        shape = (self.crosscoder.d_hidden,)
+        value = torch.as_tensor(value)
+        if (tuple(value.shape) != shape or value.dtype.is_floating_point or value.dtype.is_complex
+                or bool((value < 0).any())):
+            raise ValueError(f"tokens_since_fired takes a non-negative integer tensor of shape {shape}")
+        return value
 
     def auxk_state(self):
         """The last step's AuxK state (synchronises): aux_acts ([batch, dict_size], a view of the step's aux
@@ -233,13 +339,17 @@ class Trainer:
         b1, b2 = g["betas"]
         # the batch the next step will most likely train on (a buffer that can say, no column padding): its prep
         # rides in this step's encoder-half Adam launch; a next step handed anything else preps as always
-        peek = getattr(self.buffer, "peek_raw", None) if engine.PREP_IN_ADAM else None
+        # (master weights: the fp32 update carries no prep, and the next forward preps as always)
+        master = opt.master_for_update()
+        peek = getattr(self.buffer, "peek_raw", None) if engine.PREP_IN_ADAM and master is None else None
         nxt = peek() if peek is not None and cc._dp == cc.cfg["d_in"] else None
         if nxt is not None:
             nxt = (nxt[0], nxt[1] if normalize else None, getattr(self.buffer, "refresh_count", 0))
         engine.clip_and_adam(ws, P, opt.grads, opt.exp_avg, opt.exp_avg_sq, g["lr"], b1, b2, g["eps"], opt.t,
-                             side_stream=side, next_batch=nxt,
+                             side_stream=side, next_batch=nxt, master=master,
                              extra=(ws.theta, opt.theta_grad, opt.theta_m, opt.theta_v) if l0c is not None else None)
+        if master is not None:
+            opt.master_updated()
         self.scheduler.step()
         self._last_l1c = l1c
         self._last_l0c = l0c
@@ -316,6 +426,41 @@ class Trainer:
     def save(self):
         self.synchronize()
         self.crosscoder.save()
+
+    def state_dict(self):
+        """The trainer's own state, for resuming beside CrossCoder.save() (which keeps the parameters and a BatchTopK
+        threshold, format unchanged): the optimizer's state dict, step_counter, the scheduler's last_epoch and, for
+        AuxK trainers, tokens_since_fired.  Synchronises with the last step's launches."""
+        self.synchronize()
+        sd = {"optimizer": self.optimizer.state_dict(), "step_counter": self.step_counter,
+              "last_epoch": self.scheduler.last_epoch}
+        if self.auxk is not None:
+            sd["tokens_since_fired"] = self.tokens_since_fired.detach().clone()
+        return sd
+
+    def load_state_dict(self, sd):
+        """Takes state_dict()'s output of a trainer of the same cfg (ValueError on a mode, shape or dtype mismatch,
+        raised before anything is written: every entry is checked first).  The buffer's position is the caller's to
+        restore."""
+        keys = {"optimizer", "step_counter", "last_epoch"} | ({"tokens_since_fired"} if self.auxk is not None else set())
+        if not isinstance(sd, dict) or set(sd) != keys:
+            raise ValueError(f"Trainer.load_state_dict: expected the entries {sorted(keys)}, got "
+                             f"{sorted(sd) if isinstance(sd, dict) else type(sd).__name__}")
+        for k in ("step_counter", "last_epoch"):
+            if isinstance(sd[k], bool) or not isinstance(sd[k], int) or sd[k] < 0:
+                raise ValueError(f"Trainer.load_state_dict: {k!r} must be an int >= 0, got {sd[k]!r}")
+        self.optimizer.check_state_dict(sd["optimizer"])
+        if self.auxk is not None:
+            self._checked_since_fired(sd["tokens_since_fired"])
+        self.synchronize()
+        self.optimizer.load_state_dict(sd["optimizer"])
+        if self.auxk is not None:
+            self.tokens_since_fired = sd["tokens_since_fired"]
+        self.step_counter = sd["step_counter"]
+        self.scheduler.last_epoch = sd["last_epoch"]
+        lr = self.scheduler.base_lr * self.lr_lambda(self.scheduler.last_epoch)  # (as _check_abort re-derives it)
+        self.optimizer.param_groups[0]["lr"] = lr
+        self.scheduler._last_lr = [lr]
 
     def train(self):
         self.step_counter = 0

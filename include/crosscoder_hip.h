@@ -432,6 +432,17 @@ int cc_adam_step_clip(void* p, const void* g, void* m, void* v, int64_t numel, c
                       float max_norm, int emulate_bf16, float* clip_out, double lr, double beta1, double beta2,
                       double eps, int64_t step, int64_t max_blocks, int dtype, void* stream);
 
+/* The Adam step of a bf16 crosscoder trained with fp32 master weights (cfg["master_weights"]): g16 is the step's
+ * bf16 gradient, p32 / m32 / v32 the fp32 masters and moments, all `numel` flat elements.  p32 / m32 / v32 are
+ * updated in place with the bits of cc_adam_step(p32, float(g16), m32, v32, ..., CC_F32); p16 (bf16, the parameter
+ * arena the GEMMs read) receives p32 rounded to nearest even.  max_blocks as cc_adam_step's (0: one 8-element chunk
+ * per thread; > 0: grid-stride over at most that many workgroups, no LDS, for the launch beside a GEMM).  Any
+ * numel (the last numel % 8 elements are updated one per thread).  coef NULL: 1.  coef[0] < 0 (CC_CLIP_ABORTED):
+ * p16, p32, m32 and v32 stay untouched.  All five pointers 16-byte aligned. */
+int cc_adam_master_step(void* p32, const void* g16, void* m32, void* v32, void* p16, int64_t numel, const float* coef,
+                        double lr, double beta1, double beta2, double eps, int64_t step, int64_t max_blocks,
+                        void* stream);
+
 /* ---- around the step ---- */
 
 /* Buffer.refresh's shuffle (buffer.py:111-113: buffer = buffer[randperm(rows)]): dst[i] = src[perm[i]]
