@@ -67,7 +67,10 @@ int64_t cc_loss_scalars_len(int64_t B); /* floats in the `scalars` buffer of cc_
 
 /* Generic MFMA GEMM, fp32 output: C[M,N] = sum_k A(m,k) B(k,n).
  * a_layout KC: A at A[m*lda+k]; MN: A at A[k*lda+m].  b_layout KC: B at B[n*ldb+k];
- * MN: B at B[k*ldb+n].  (Test/diagnostic entry; the fused entries below use the same kernel.) */
+ * MN: B at B[k*ldb+n].  (Test/diagnostic entry; the fused entries below use the same kernel.)
+ * An operand's contiguous dimension (K for KC; M for an MN A, N for an MN B) and lda / ldb are whole 16-byte
+ * vectors (multiples of 8 in bf16, 4 in fp32), N % 4 == 0 and ldc % 4 == 0, else CC_ERR_SHAPE / CC_ERR_ALIGN:
+ * M = 1 runs with a KC A only. */
 int cc_gemm_f32out(const void* A, int a_layout, int64_t lda, const void* Bm, int b_layout, int64_t ldb,
                    float* C, int64_t ldc, int64_t M, int64_t N, int64_t K, int dtype, void* stream);
 
