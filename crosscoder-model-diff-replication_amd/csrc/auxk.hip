@@ -4,7 +4,7 @@
 //                   (pass 1 -> partial slabs, the squared column sums, the scalar finaliser, pass 2 -> g_aux)
 //   cc_add_rows     dst = dtype(float(dst) + float(src))
 // No float atomics anywhere: every sum goes through partial slabs added in a fixed order.
-#include "cc_common.h"
+#include "mask_common.h"
 
 namespace cc {
 
@@ -27,8 +27,7 @@ __global__ __launch_bounds__(DU_NT) void dead_update_kernel(const float* __restr
     if (was_dead) was_dead[l] = old >= dead_after ? 1 : 0;
     mine += (l < h_real && now >= dead_after) ? 1 : 0;  // (padding latents never fire: not counted)
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o, 64);
+  mine = (int)wave_sum_u((uint32_t)mine);
   if ((tid & 63) == 0) wsum[tid >> 6] = mine;
   __syncthreads();
   if (tid == 0) {

@@ -3,8 +3,8 @@
 // (or the activation itself), plus the step's side outputs (column-sum partials, selected counts), the per-row
 // counts and the threshold score; and the inference form, one pass that keeps score >= *theta.  gfx950.
 //
-// Positive floats order as their bit patterns, so selection is a radix select on integer keys over the whole
-// [B][h] extent (key: the bits of a score > 0 of an activation > 0, else 0: ineligible).  Keys are the 16 element
+// Eligibility, the tie order and the fixed sums are mask_common.h's rules.  Selection is a radix select on integer
+// keys over the whole [B][h] extent (key: the bits of a score > 0 of an activation > 0, else 0).  Keys are the 16 element
 // bits for unweighted bf16 (digits 8 + 8) and the 32 fp32 score bits otherwise (bit 31 is clear: digits
 // 11 + 12 + 8, so three reads fix the threshold instead of four).
 // The phases are separate launches on the one stream; no workgroup waits for another inside a kernel:
@@ -15,22 +15,20 @@
 //   select<p>  one workgroup scans the global histogram from the top for the digit that holds the wanted rank.
 //   mask       admits every key above the threshold T and the first `need` keys equal to T in flat-index order:
 //              a workgroup's tie base is the sum of the slab's column (T's last digit) over the workgroups before
-//              it, its own ties are ordered by a prefix count across lanes, then waves (only when some tie at T is
-//              left out; otherwise key >= T decides and no workgroup barrier runs in the loop).
+//              it, its own ties are ordered by CC_BLOCK_EXCL_SCAN (only when some tie at T is left out; otherwise
+//              key >= T decides and no workgroup barrier runs in the loop).
 // Work split (the same in every phase, so the slab rows are the mask pass' workgroups): the flat extent is cut into
 // segments of 1024 lanes x 8 consecutive columns in flat-index order -- h >= 8192: a segment is 8192 columns of one
 // row; below: 1024 / (h / 8) whole rows -- and a workgroup takes a contiguous run of segments, so flat-index order
 // is (workgroup, segment, lane, element) and a lane owns the same columns in every segment.
 // Column sums: wide rows add the selected values to the workgroup's own partial row (zeroed and updated by the lane
-// that owns the column: program order); narrow rows keep 8 sums per lane and fold the lanes that share a column
-// through LDS in lane order.  No float atomics: every output is fixed by (B, h) and the input alone.
-#include "cc_common.h"
+// that owns the column); narrow rows keep 8 sums per lane and fold the lanes that share a column (fold_cols8).
+#include "mask_common.h"
 
 namespace cc {
 
 constexpr int BT_NT = 1024, BT_NW = BT_NT / 64, BT_CH = BT_NT * 8;
 constexpr int BT_MAX_G = 256;       // workgroups (= column-sum partial rows = count partials = slab rows)
-constexpr int BT_MAX_H = 1 << 17;
 constexpr int BT_HIST_WORDS = 8192;  // LDS histogram words: bins x copies
 constexpr int BT_GBINS = 4096;       // global histogram words per pass
 constexpr int BT_LAST_BINS = 256;    // the last digit is 8 bits in both plans
@@ -74,87 +72,20 @@ static BtMap bt_map(int64_t B, int64_t h) {
   return m;
 }
 
-struct BtVec { uint4 q[2]; };
-
-template <int DT> CC_DEV BtVec bt_load(const void* base, int64_t e, bool ok) {
-  BtVec v;
-  v.q[1] = uint4{0u, 0u, 0u, 0u};
-  if constexpr (DT == CC_BF16) {
-    v.q[0] = ok ? *(const uint4*)((const bf16_t*)base + e) : uint4{0u, 0u, 0u, 0u};
-  } else {
-    v.q[0] = ok ? *(const uint4*)((const float*)base + e) : uint4{0u, 0u, 0u, 0u};
-    v.q[1] = ok ? *(const uint4*)((const float*)base + e + 4) : uint4{0u, 0u, 0u, 0u};
-  }
-  return v;
-}
-
-template <int DT> CC_DEV void bt_elem_bits(const BtVec& v, uint32_t (&u)[8]) {
-  if constexpr (DT == CC_BF16) {
-    const uint32_t w[4] = {v.q[0].x, v.q[0].y, v.q[0].z, v.q[0].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      u[2 * j] = w[j] & 0xffffu;
-      u[2 * j + 1] = w[j] >> 16;
-    }
-  } else {
-    u[0] = v.q[0].x; u[1] = v.q[0].y; u[2] = v.q[0].z; u[3] = v.q[0].w;
-    u[4] = v.q[1].x; u[5] = v.q[1].y; u[6] = v.q[1].z; u[7] = v.q[1].w;
-  }
-}
-
-template <int DT> CC_DEV void bt_store(void* base, int64_t e, const uint32_t (&u)[8]) {
-  if constexpr (DT == CC_BF16) {
-    *(uint4*)((bf16_t*)base + e) = uint4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
-  } else {
-    *(uint4*)((float*)base + e) = uint4{u[0], u[1], u[2], u[3]};
-    *(uint4*)((float*)base + e + 4) = uint4{u[4], u[5], u[6], u[7]};
-  }
-}
-
-struct BtW { float4 a, b; };
-CC_DEV BtW bt_load_w(const float* weight, int col, bool ok) {
-  BtW w;
-  w.a = ok ? *(const float4*)(weight + col) : float4{0.f, 0.f, 0.f, 0.f};
-  w.b = ok ? *(const float4*)(weight + col + 4) : float4{0.f, 0.f, 0.f, 0.f};
-  return w;
-}
-
-// bits > 0 as a float of EB bits' width (sign clear, not zero, not NaN; +inf and subnormals count), else 0
-template <int EB> CC_DEV uint32_t bt_pos(uint32_t u) {
-  constexpr uint32_t INF = EB == 16 ? 0x7F80u : 0x7F800000u;
-  return (u - 1u) < INF ? u : 0u;
-}
-template <int DT> CC_DEV float bt_float(uint32_t u) { return __uint_as_float(DT == CC_BF16 ? u << 16 : u); }
-
 // the 8 keys of a lane's elements: weighted, the bits of the fp32 product (one IEEE multiply) where both the
 // activation and the product are > 0
-template <int DT, bool W> CC_DEV void bt_keys(const uint32_t (&u)[8], const BtW& w, uint32_t (&key)[8]) {
-  constexpr int EB = DT == CC_BF16 ? 16 : 32;
+template <int DT, bool W> CC_DEV void bt_keys(const uint32_t (&u)[8], const Cols8& w, uint32_t (&key)[8]) {
+  constexpr int EB = ELEM_BITS<DT>;
   if constexpr (!W) {
 #pragma unroll
-    for (int j = 0; j < 8; ++j) key[j] = bt_pos<EB>(u[j]);
+    for (int j = 0; j < 8; ++j) key[j] = pos_key<EB>(u[j]);
   } else {
-    const float wj[8] = {w.a.x, w.a.y, w.a.z, w.a.w, w.b.x, w.b.y, w.b.z, w.b.w};
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const uint32_t s = bt_pos<32>(__float_as_uint(__fmul_rn(bt_float<DT>(u[j]), wj[j])));
-      key[j] = bt_pos<EB>(u[j]) ? s : 0u;
+      const uint32_t s = pos_key<32>(__float_as_uint(__fmul_rn(bits_float<DT>(u[j]), w.v[j])));
+      key[j] = pos_key<EB>(u[j]) ? s : 0u;
     }
   }
-}
-
-CC_DEV uint32_t bt_wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-CC_DEV uint32_t bt_wave_sum(uint32_t v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
 }
 
 // a lane's place in segment s: (row, first column, inside the extent)
@@ -195,17 +126,17 @@ __global__ __launch_bounds__(BT_NT) void bt_hist_kernel(const void* acts, int64_
   const int s0 = g * m.spg, s1 = min(m.nseg, s0 + m.spg);
 
   BtPos pc = bt_pos_of(m, s0, tid, r_in, c_in, B, h);
-  BtVec cur = bt_load<DT>(acts, (int64_t)pc.row * ld + pc.col, pc.ok);
-  BtW wc = {};
-  if constexpr (W) wc = bt_load_w(weight, pc.col, pc.ok);
+  Vec8<DT> cur = load_vec8<DT>(acts, (int64_t)pc.row * ld + pc.col, pc.ok);
+  Cols8 wc = {};
+  if constexpr (W) wc = load_cols8(weight, pc.col, pc.ok);
   for (int s = s0; s < s1; ++s) {
     const BtPos pn = bt_pos_of(m, s + 1, tid, r_in, c_in, B, h);
     const bool okn = pn.ok && s + 1 < s1;
-    const BtVec nxt = bt_load<DT>(acts, (int64_t)pn.row * ld + pn.col, okn);
-    BtW wn = {};
-    if constexpr (W) wn = bt_load_w(weight, pn.col, okn);
+    const Vec8<DT> nxt = load_vec8<DT>(acts, (int64_t)pn.row * ld + pn.col, okn);
+    Cols8 wn = {};
+    if constexpr (W) wn = load_cols8(weight, pn.col, okn);
     uint32_t u[8], key[8];
-    bt_elem_bits<DT>(cur, u);
+    vec8_bits<DT>(cur, u);
     bt_keys<DT, W>(u, wc, key);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
@@ -249,16 +180,7 @@ __global__ __launch_bounds__(256) void bt_select_kernel(uint32_t* __restrict__ w
     cnt[j] = ghist[NB - 1 - tid * PER - j];
     local += cnt[j];
   }
-  const uint32_t incl = bt_wave_incl_scan(local, lane);
-  if (lane == 63) wsum[w] = incl;
-  __syncthreads();
-  uint32_t before = incl - local, total = 0u;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const uint32_t t = wsum[q];
-    if (q < w) before += t;
-    total += t;
-  }
+  CC_BLOCK_EXCL_SCAN(4, local, lane, w, wsum, before, total);
   if constexpr (PASS == 0) {
     eligible = total;
     n_sel = (int64_t)eligible < n_keep ? eligible : (uint32_t)n_keep;
@@ -338,7 +260,7 @@ __global__ __launch_bounds__(BT_NT) void bt_mask_kernel(const void* acts, int64_
     ordered = need < ws[4];  // (uniform) some key equal to T is left out: flat-index order decides
     if (ordered) {
       const uint32_t v = tid < g ? ws[BT_HEAD_WORDS + tid * BT_LAST_BINS + (T & (BT_LAST_BINS - 1))] : 0u;
-      const uint32_t t = bt_wave_sum(v);
+      const uint32_t t = wave_sum_u(v);
       if (lane == 0) wred[w] = t;
       __syncthreads();
 #pragma unroll
@@ -351,28 +273,21 @@ __global__ __launch_bounds__(BT_NT) void bt_mask_kernel(const void* acts, int64_
   float acc[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
-  if (m.wide && mypart)
-    for (int c = 0; c < m.S; ++c) {
-      const int col = c * BT_CH + tid * 8;
-      if (col < h) {
-        *(float4*)(mypart + col) = float4{0.f, 0.f, 0.f, 0.f};
-        *(float4*)(mypart + col + 4) = float4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+  if (m.wide && mypart) zero_cols(mypart, m.S, BT_CH, tid, h);
   uint32_t selected = 0u;
 
   BtPos pc = bt_pos_of(m, s0, tid, r_in, c_in, B, h);
-  BtVec cur = bt_load<DT>(acts, (int64_t)pc.row * ld + pc.col, pc.ok);
-  BtW wc = {};
-  if constexpr (W) wc = bt_load_w(weight, pc.col, pc.ok);
+  Vec8<DT> cur = load_vec8<DT>(acts, (int64_t)pc.row * ld + pc.col, pc.ok);
+  Cols8 wc = {};
+  if constexpr (W) wc = load_cols8(weight, pc.col, pc.ok);
   for (int s = s0; s < s1; ++s) {
     const BtPos pn = bt_pos_of(m, s + 1, tid, r_in, c_in, B, h);
     const bool okn = pn.ok && s + 1 < s1;
-    const BtVec nxt = bt_load<DT>(acts, (int64_t)pn.row * ld + pn.col, okn);
-    BtW wn = {};
-    if constexpr (W) wn = bt_load_w(weight, pn.col, okn);
+    const Vec8<DT> nxt = load_vec8<DT>(acts, (int64_t)pn.row * ld + pn.col, okn);
+    Cols8 wn = {};
+    if constexpr (W) wn = load_cols8(weight, pn.col, okn);
     uint32_t u[8], key[8];
-    bt_elem_bits<DT>(cur, u);
+    vec8_bits<DT>(cur, u);
     bt_keys<DT, W>(u, wc, key);  // (outside the extent: zeros, key 0)
 
     uint32_t eq = 0u;
@@ -380,16 +295,7 @@ __global__ __launch_bounds__(BT_NT) void bt_mask_kernel(const void* acts, int64_
       uint32_t mine = 0u;
 #pragma unroll
       for (int j = 0; j < 8; ++j) mine += key[j] == T ? 1u : 0u;
-      const uint32_t incl = bt_wave_incl_scan(mine, lane);
-      if (lane == 63) wtot[s & 1][w] = incl;
-      __syncthreads();
-      uint32_t before = incl - mine, all = 0u;
-#pragma unroll
-      for (int q = 0; q < BT_NW; ++q) {
-        const uint32_t t = wtot[s & 1][q];
-        if (q < w) before += t;
-        all += t;
-      }
+      CC_BLOCK_EXCL_SCAN(BT_NW, mine, lane, w, wtot[s & 1], before, all);
       eq = eq_base + before;
       eq_base += all;
     }
@@ -407,17 +313,17 @@ __global__ __launch_bounds__(BT_NT) void bt_mask_kernel(const void* acts, int64_
       o[j] = sel ? u[j] : 0u;
       cnt += sel ? 1u : 0u;
       if (m.wide) {
-        if (sel && mypart) mypart[pc.col + j] += bt_float<DT>(u[j]);
+        if (sel && mypart) mypart[pc.col + j] += bits_float<DT>(u[j]);
       } else {
-        acc[j] += sel ? bt_float<DT>(u[j]) : 0.f;
+        acc[j] += sel ? bits_float<DT>(u[j]) : 0.f;
       }
     }
-    if (acts_out && pc.ok) bt_store<DT>(acts_out, (int64_t)pc.row * ld + pc.col, o);
+    if (acts_out && pc.ok) store_bits8<DT>(acts_out, (int64_t)pc.row * ld + pc.col, o);
     selected += cnt;
     if (row_count) {
       const int r0 = __builtin_amdgcn_readfirstlane(pc.row);
       if (__builtin_amdgcn_ballot_w64(cnt != 0u && pc.row != r0) == 0ull) {  // the wave's selected share one row
-        const uint32_t t = bt_wave_sum(cnt);
+        const uint32_t t = wave_sum_u(cnt);
         if (lane == 0 && t) atomicAdd(row_count + r0, (int)t);
       } else if (cnt) {
         atomicAdd(row_count + pc.row, (int)cnt);
@@ -428,32 +334,11 @@ __global__ __launch_bounds__(BT_NT) void bt_mask_kernel(const void* acts, int64_
     wc = wn;
   }
 
-  if (!m.wide && mypart) {  // the lanes that share a column (one per row of a segment), in lane order
-#pragma unroll
-    for (int j = 0; j < 8; ++j) red[tid * 8 + j] = acc[j];
-    __syncthreads();
-    if (tid < m.U) {
-      float t[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) t[j] = 0.f;
-      for (int r = 0; r < m.RP; ++r)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] += red[(r * m.U + tid) * 8 + j];
-      *(float4*)(mypart + c_in) = float4{t[0], t[1], t[2], t[3]};
-      *(float4*)(mypart + c_in + 4) = float4{t[4], t[5], t[6], t[7]};
-    }
-  }
+  // the lanes that share a column: one per row of a segment
+  if (!m.wide && mypart) fold_cols8(acc, red, m.U, m.RP, tid, mypart, c_in);
   if (l0_part) {
-    const uint32_t t = bt_wave_sum(selected);
     __syncthreads();
-    if (lane == 0) wred[w] = t;
-    __syncthreads();
-    if (tid == 0) {
-      uint32_t all = 0u;
-#pragma unroll
-      for (int q = 0; q < BT_NW; ++q) all += wred[q];
-      l0_part[g] = (float)all;
-    }
+    count_to_part<BT_NW>(selected, wred, l0_part + g);
   }
 }
 
@@ -489,55 +374,32 @@ static void bt_launch_theta(const void* acts, int64_t ld, int64_t B, int64_t h, 
                      weight, m, (const uint32_t*)nullptr, theta, acts_out, colsum_part, l0_part, row_count);
 }
 
-static int bt_check(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* weight,
-                    const void* acts_out, const float* colsum_part, const float* l0_part, bool any_out,
-                    const void* needed, bool shape_ok = true) {
-  if (B < 1 || h < 8 || (h & 7) || (ld & 7) || ld < h || !shape_ok) return CC_ERR_SHAPE;
-  if (!acts || !any_out || !needed) return CC_ERR_NULL;
-  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
-  if (h > BT_MAX_H || B > ((int64_t)1 << 31) / h) return CC_ERR_TOO_LARGE;
-  if (((uintptr_t)acts | (uintptr_t)acts_out | (uintptr_t)colsum_part | (uintptr_t)weight) & 15) return CC_ERR_ALIGN;
-  if ((uintptr_t)l0_part & 3) return CC_ERR_ALIGN;
-  return CC_OK;
-}
-
 }  // namespace cc
 
 using namespace cc;
 
 extern "C" {
 
-static bool bt_dims_ok(int64_t B, int64_t h) {
-  return B >= 1 && h >= 8 && !(h & 7) && h <= BT_MAX_H && B <= ((int64_t)1 << 31) / h;
-}
-
-int64_t cc_batch_topk_part_rows(int64_t B, int64_t h) { return bt_dims_ok(B, h) ? bt_map(B, h).G : 0; }
-int64_t cc_batch_topk_l0_parts(int64_t B, int64_t h) { return bt_dims_ok(B, h) ? bt_map(B, h).G : 0; }
+int64_t cc_batch_topk_part_rows(int64_t B, int64_t h) { return dims_ok(B, h) ? bt_map(B, h).G : 0; }
+int64_t cc_batch_topk_l0_parts(int64_t B, int64_t h) { return dims_ok(B, h) ? bt_map(B, h).G : 0; }
 
 int64_t cc_batch_topk_ws_bytes(int64_t B, int64_t h, int dtype, int weighted) {
   (void)weighted;  // (one layout for both key widths)
-  if (!bt_dims_ok(B, h) || (dtype != CC_BF16 && dtype != CC_F32)) return 0;
+  if (!dims_ok(B, h) || (dtype != CC_BF16 && dtype != CC_F32)) return 0;
   return (int64_t)sizeof(uint32_t) * (BT_HEAD_WORDS + (int64_t)bt_map(B, h).G * BT_LAST_BINS);
 }
 
 int cc_batch_topk(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* weight, int64_t n_keep,
                   void* acts_out, float* colsum_part, float* l0_part, int32_t* row_count, uint32_t* info,
                   float* threshold_ema, float beta, void* ws, int64_t ws_bytes, void* stream) {
-  const int rc = bt_check(acts, ld, B, h, dtype, weight, acts_out, colsum_part, l0_part,
-                          acts_out || info || row_count, ws, n_keep >= 1 && (!threshold_ema || (beta >= 0.f && beta < 1.f)));
+  const int rc = rows_check(ld, B, h, dtype, n_keep >= 1 && (!threshold_ema || (beta >= 0.f && beta < 1.f)),
+                            acts && (acts_out || info || row_count) && ws, true, {acts, acts_out, colsum_part, weight},
+                            {l0_part, ws, info, row_count, threshold_ema});
   if (rc != CC_OK) return rc;
-  if (((uintptr_t)ws | (uintptr_t)info | (uintptr_t)row_count | (uintptr_t)threshold_ema) & 3) return CC_ERR_ALIGN;
   if (ws_bytes < cc_batch_topk_ws_bytes(B, h, dtype, weight != nullptr)) return CC_ERR_SHAPE;
-  hipStream_t st = (hipStream_t)stream;
-#define BT_GO(DT, W)                                                                                                  \
-  bt_launch<DT, W>(acts, ld, B, h, weight, n_keep, acts_out, colsum_part, l0_part, row_count, info, threshold_ema, beta, \
-                   (uint32_t*)ws, st)
-  if (dtype == CC_BF16) {
-    if (weight) BT_GO(CC_BF16, true); else BT_GO(CC_BF16, false);
-  } else {
-    if (weight) BT_GO(CC_F32, true); else BT_GO(CC_F32, false);
-  }
-#undef BT_GO
+  const auto launch = weight ? CC_BY_DTYPE(bt_launch, dtype, true) : CC_BY_DTYPE(bt_launch, dtype, false);
+  launch(acts, ld, B, h, weight, n_keep, acts_out, colsum_part, l0_part, row_count, info, threshold_ema, beta,
+         (uint32_t*)ws, (hipStream_t)stream);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
@@ -545,17 +407,11 @@ int cc_batch_topk(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype,
 int cc_threshold_mask(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, const float* weight,
                       const float* theta, void* acts_out, float* colsum_part, float* l0_part, int32_t* row_count,
                       void* stream) {
-  const int rc = bt_check(acts, ld, B, h, dtype, weight, acts_out, colsum_part, l0_part, acts_out || row_count, theta);
+  const int rc = rows_check(ld, B, h, dtype, true, acts && (acts_out || row_count) && theta, true,
+                            {acts, acts_out, colsum_part, weight}, {l0_part, theta, row_count});
   if (rc != CC_OK) return rc;
-  if (((uintptr_t)theta | (uintptr_t)row_count) & 3) return CC_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-#define BT_GO(DT, W) bt_launch_theta<DT, W>(acts, ld, B, h, weight, theta, acts_out, colsum_part, l0_part, row_count, st)
-  if (dtype == CC_BF16) {
-    if (weight) BT_GO(CC_BF16, true); else BT_GO(CC_BF16, false);
-  } else {
-    if (weight) BT_GO(CC_F32, true); else BT_GO(CC_F32, false);
-  }
-#undef BT_GO
+  const auto launch = weight ? CC_BY_DTYPE(bt_launch_theta, dtype, true) : CC_BY_DTYPE(bt_launch_theta, dtype, false);
+  launch(acts, ld, B, h, weight, theta, acts_out, colsum_part, l0_part, row_count, (hipStream_t)stream);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }

@@ -2,8 +2,8 @@
 // acts_out) to each row's k largest positive values, plus the compact (latent, value) pairs and the side
 // outputs of the step (column-sum partials and selected counts of the masked activations).  gfx950.
 //
-// Positive floats order as their bit patterns, so selection is a radix select on integer keys (the element's
-// bits when it is > 0, else 0: ineligible), 8-bit digits from the top: 2 passes for bf16, 4 for fp32.
+// Eligibility, the tie order and the fixed sums are mask_common.h's rules.  Selection is a radix select on the
+// integer keys (pos_key: 0 is ineligible), 8-bit digits from the top: 2 passes for bf16, 4 for fp32.
 // A workgroup takes rows in turn (row = blockIdx.x + i * gridDim.x); lane t owns the 8 consecutive columns
 // c * 8 * NT + 8 t of every chunk c (one 16-B / 32-B load), so index order is (chunk, lane, element).
 //   NCH > 0: the row (NCH chunks) stays in registers over all passes, the next row is loaded while this one is
@@ -15,79 +15,24 @@
 // the address's bank is the lane's own, so integer LDS atomics of one half-wave never collide), the copies are
 // summed, and every wave scans the 256 totals from the top for the digit that holds the wanted rank.
 // The last pass admits every key above the threshold T and the first `need` keys equal to T in index order
-// (per chunk: a prefix count across lanes, then across waves), which is also each element's output slot.
-// No float atomics: the partial rows and counts are fixed by (B, h) and the input alone.
+// (per chunk: CC_BLOCK_EXCL_SCAN), which is also each element's output slot.
 //
 // AUX (cc_auxk_rows, the AuxK dead-latent loss): the same selection with a column predicate -- an element's key
 // is 0 unless since_fired[column] >= dead_after.  A lane owns the same columns in every row, so the predicate is
 // loaded once per workgroup (one int64 per owned column) and kept as bits over the row loop: 8 NCH bits in one
 // register, or (NCH = 0, up to 16 chunks) 128 bits in two 64-bit registers.  It writes the dense output and the
 // row counts only.
-#include "cc_common.h"
+#include "mask_common.h"
 
 namespace cc {
 
 constexpr int TK_COPIES = 32;
 constexpr int TK_BINS = 256;
-constexpr int TK_MAX_H = 1 << 17;
-
-template <int DT> struct TkVec { uint4 q[DT == CC_F32 ? 2 : 1]; };
-
-template <int DT> CC_DEV TkVec<DT> tk_load(const void* base, int64_t e, bool ok) {
-  TkVec<DT> v;
-  if constexpr (DT == CC_BF16) {
-    v.q[0] = ok ? *(const uint4*)((const bf16_t*)base + e) : uint4{0u, 0u, 0u, 0u};
-  } else {
-    v.q[0] = ok ? *(const uint4*)((const float*)base + e) : uint4{0u, 0u, 0u, 0u};
-    v.q[1] = ok ? *(const uint4*)((const float*)base + e + 4) : uint4{0u, 0u, 0u, 0u};
-  }
-  return v;
-}
-
-// the 8 elements' bits
-template <int DT> CC_DEV void tk_bits(const TkVec<DT>& v, uint32_t (&u)[8]) {
-  if constexpr (DT == CC_BF16) {
-    const uint32_t w[4] = {v.q[0].x, v.q[0].y, v.q[0].z, v.q[0].w};
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      u[2 * j] = w[j] & 0xffffu;
-      u[2 * j + 1] = w[j] >> 16;
-    }
-  } else {
-    u[0] = v.q[0].x; u[1] = v.q[0].y; u[2] = v.q[0].z; u[3] = v.q[0].w;
-    u[4] = v.q[1].x; u[5] = v.q[1].y; u[6] = v.q[1].z; u[7] = v.q[1].w;
-  }
-}
-
-// the key: the bits of an element > 0 (sign clear, not zero, not NaN; +inf and subnormals count), else 0
-template <int DT> CC_DEV uint32_t tk_key(uint32_t u) {
-  constexpr uint32_t INF = DT == CC_BF16 ? 0x7F80u : 0x7F800000u;
-  return (u - 1u) < INF ? u : 0u;
-}
-template <int DT> CC_DEV float tk_float(uint32_t u) { return __uint_as_float(DT == CC_BF16 ? u << 16 : u); }
-
-template <int DT> CC_DEV void tk_store(void* base, int64_t e, const uint32_t (&u)[8]) {
-  if constexpr (DT == CC_BF16) {
-    *(uint4*)((bf16_t*)base + e) = uint4{u[0] | (u[1] << 16), u[2] | (u[3] << 16), u[4] | (u[5] << 16), u[6] | (u[7] << 16)};
-  } else {
-    *(uint4*)((float*)base + e) = uint4{u[0], u[1], u[2], u[3]};
-    *(uint4*)((float*)base + e + 4) = uint4{u[4], u[5], u[6], u[7]};
-  }
-}
-
-CC_DEV uint32_t tk_wave_incl_scan(uint32_t v, int lane) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const uint32_t t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
 
 // the key under the column predicate: db holds the dead bits of the 8 columns of this lane's chunk
 template <int DT, bool AUX> CC_DEV uint32_t tk_key_if(uint32_t u, uint32_t db, int j) {
-  if constexpr (AUX) return (db >> j) & 1u ? tk_key<DT>(u) : 0u;
-  else return tk_key<DT>(u);
+  if constexpr (AUX) return (db >> j) & 1u ? pos_key<ELEM_BITS<DT>>(u) : 0u;
+  else return pos_key<ELEM_BITS<DT>>(u);
 }
 
 // (acts and acts_out may be the same buffer: no __restrict__ on them)
@@ -140,37 +85,30 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
 #pragma unroll
     for (int j = 0; j < 8; ++j) acc[c][j] = 0.f;
   float* const mypart = colsum_part ? colsum_part + (int64_t)blockIdx.x * h : nullptr;
-  if (!REG && mypart)
-    for (int c = 0; c < nch; ++c) {
-      const int col = c * CH + tid * 8;
-      if (col < h) {
-        *(float4*)(mypart + col) = float4{0.f, 0.f, 0.f, 0.f};
-        *(float4*)(mypart + col + 4) = float4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
+  if (!REG && mypart) zero_cols(mypart, nch, CH, tid, h);
   uint32_t selected_rows = 0u;  // selected elements over this workgroup's rows
   __syncthreads();
 
-  TkVec<DT> cur[NR];
+  Vec8<DT> cur[NR];
   if constexpr (REG) {
     if ((int)blockIdx.x < B) {
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int col = c * CH + tid * 8;
-        cur[c] = tk_load<DT>(acts, (int64_t)blockIdx.x * ld + col, col < h);
+        cur[c] = load_vec8<DT>(acts, (int64_t)blockIdx.x * ld + col, col < h);
       }
     }
   }
 
   for (int row = blockIdx.x; row < B; row += gridDim.x) {
     const int64_t roff = (int64_t)row * ld;
-    TkVec<DT> nxt[NR];
+    Vec8<DT> nxt[NR];
     if constexpr (REG) {
       const int nrow = row + gridDim.x;
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int col = c * CH + tid * 8;
-        nxt[c] = tk_load<DT>(acts, (int64_t)nrow * ld + col, nrow < B && col < h);
+        nxt[c] = load_vec8<DT>(acts, (int64_t)nrow * ld + col, nrow < B && col < h);
       }
     }
     // f(c, col, u): chunk c's 8 elements of this lane (column col .. col + 7 < h)
@@ -180,14 +118,14 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
         for (int c = 0; c < NCH; ++c) {
           const int col = c * CH + tid * 8;
           uint32_t u[8];
-          tk_bits<DT>(cur[c], u);
+          vec8_bits<DT>(cur[c], u);
           f(c, col, u);
         }
       } else {
         for (int c = 0; c < nch; ++c) {
           const int col = c * CH + tid * 8;
           uint32_t u[8];
-          tk_bits<DT>(tk_load<DT>(acts, roff + col, col < h), u);
+          vec8_bits<DT>(load_vec8<DT>(acts, roff + col, col < h), u);
           f(c, col, u);
         }
       }
@@ -225,7 +163,7 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
 #pragma unroll
       for (int j = 0; j < 4; ++j) cnt[j] = tot[255 - 4 * lane - j];
       const uint32_t local = cnt[0] + cnt[1] + cnt[2] + cnt[3];
-      const uint32_t incl = tk_wave_incl_scan(local, lane);
+      const uint32_t incl = wave_incl_scan(local, lane);
       if (p == 0) {
         const uint32_t eligible = __shfl(incl, 63, 64);
         n_sel = eligible < (uint32_t)k ? eligible : (uint32_t)k;
@@ -261,19 +199,10 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
         key[j] = tk_key_if<DT, AUX>(u[j], db, j);
         mine += key[j] > T ? 0x10000u : key[j] == T ? 1u : 0u;
       }
-      const uint32_t incl = tk_wave_incl_scan(mine, lane);
-      if (lane == 63) wtot[c & 1][w] = incl;
-      __syncthreads();
-      uint32_t before = incl - mine, all = 0u;
-#pragma unroll
-      for (int q = 0; q < NW; ++q) {
-        const uint32_t t = wtot[c & 1][q];
-        if (q < w) before += t;
-        all += t;
-      }
+      CC_BLOCK_EXCL_SCAN(NW, mine, lane, w, wtot[c & 1], before, all);
       uint32_t gt = base_gt + (before >> 16), eq = base_eq + (before & 0xffffu);
       base_gt += all >> 16;
-      base_eq += all & 0xffffu;
+      base_eq += (all & 0xffffu);
       if (col < h) {
         uint32_t o[8];
 #pragma unroll
@@ -288,14 +217,14 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
             else ((uint32_t*)val_out)[(int64_t)row * k + slot] = u[j];
           }
           if constexpr (REG) {
-            acc[c][j] += sel ? tk_float<DT>(u[j]) : 0.f;
+            acc[c][j] += sel ? bits_float<DT>(u[j]) : 0.f;
           } else {
-            if (sel && mypart) mypart[col + j] += tk_float<DT>(u[j]);
+            if (sel && mypart) mypart[col + j] += bits_float<DT>(u[j]);
           }
           gt += is_gt ? 1u : 0u;
           eq += is_eq ? 1u : 0u;
         }
-        if (acts_out) tk_store<DT>(acts_out, roff + col, o);
+        if (acts_out) store_bits8<DT>(acts_out, roff + col, o);
       }
     });
     if (idx_out)
@@ -319,10 +248,7 @@ __global__ __launch_bounds__(NT) void topk_rows_kernel(const void* acts, int64_t
 #pragma unroll
       for (int c = 0; c < NCH; ++c) {
         const int col = c * CH + tid * 8;
-        if (col < h) {
-          *(float4*)(mypart + col) = float4{acc[c][0], acc[c][1], acc[c][2], acc[c][3]};
-          *(float4*)(mypart + col + 4) = float4{acc[c][4], acc[c][5], acc[c][6], acc[c][7]};
-        }
+        if (col < h) store_cols8(mypart + col, acc[c]);
       }
     }
   }
@@ -335,37 +261,21 @@ static int64_t tk_groups(int64_t B, int64_t h) {
   return B < g ? B : g;
 }
 
-template <int DT>
+// the form by h (AUX: cc_auxk_rows, which passes no pairs and no partials)
+template <int DT, bool AUX>
 static void tk_launch(const void* acts, int64_t ld, int64_t B, int64_t h, int k, void* acts_out, int32_t* idx_out,
-                      void* val_out, float* colsum_part, float* l0_part, hipStream_t st) {
-  const dim3 grid((unsigned)tk_groups(B, h));
-#define TK_GO(NT, NCH)                                                                                              \
-  hipLaunchKernelGGL((topk_rows_kernel<DT, NT, NCH>), grid, dim3(NT), 0, st, acts, ld, (int)B, (int)h, k, acts_out, \
-                     idx_out, val_out, colsum_part, l0_part)
+                      void* val_out, float* colsum_part, float* l0_part, const int64_t* since_fired, int64_t dead_after,
+                      int32_t* row_count, hipStream_t st) {
   // (fp32 rows beyond one chunk re-read: two chunks of fp32 in registers spill at the 128 VGPRs of 16 waves)
-  if (h <= 2048) TK_GO(256, 1);
-  else if (h <= 8192) TK_GO(1024, 1);
-  else if (DT == CC_BF16 && h <= 16384) {
-    if constexpr (DT == CC_BF16) TK_GO(1024, 2);
-  } else TK_GO(1024, 0);
-#undef TK_GO
-}
-
-template <int DT>
-static void ak_launch(const void* acts, int64_t ld, int64_t B, int64_t h, int k, const int64_t* since_fired,
-                      int64_t dead_after, void* aux_out, int32_t* row_count, hipStream_t st) {
-  const dim3 grid((unsigned)tk_groups(B, h));
-#define AK_GO(NT, NCH)                                                                                                \
-  hipLaunchKernelGGL((topk_rows_kernel<DT, NT, NCH, true>), grid, dim3(NT), 0, st, acts, ld, (int)B, (int)h, k, aux_out, \
-                     (int32_t*)nullptr, (void*)nullptr, (float*)nullptr, (float*)nullptr, since_fired, dead_after,    \
-                     row_count)
-  // (the four forms of tk_launch, by h)
-  if (h <= 2048) AK_GO(256, 1);
-  else if (h <= 8192) AK_GO(1024, 1);
-  else if (DT == CC_BF16 && h <= 16384) {
-    if constexpr (DT == CC_BF16) AK_GO(1024, 2);
-  } else AK_GO(1024, 0);
-#undef AK_GO
+  constexpr int REG_H = DT == CC_BF16 ? 16384 : 8192;  // the widest row kept in registers
+  auto kern = topk_rows_kernel<DT, 256, 1, AUX>;
+  if (h > 2048) kern = topk_rows_kernel<DT, 1024, 1, AUX>;
+  if constexpr (DT == CC_BF16) {
+    if (h > 8192) kern = topk_rows_kernel<DT, 1024, 2, AUX>;
+  }
+  if (h > REG_H) kern = topk_rows_kernel<DT, 1024, 0, AUX>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)tk_groups(B, h)), dim3(h <= 2048 ? 256 : 1024), 0, st, acts, ld, (int)B,
+                     (int)h, k, acts_out, idx_out, val_out, colsum_part, l0_part, since_fired, dead_after, row_count);
 }
 
 }  // namespace cc
@@ -379,31 +289,22 @@ int64_t cc_topk_l0_parts(int64_t B, int64_t h) { return B < 1 || h < 1 ? 0 : tk_
 
 int cc_topk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k, void* acts_out,
                  int32_t* idx_out, void* val_out, float* colsum_part, float* l0_part, void* stream) {
-  if (B < 1 || h < 8 || (h & 7) || (ld & 7) || ld < h || k < 1 || k > h) return CC_ERR_SHAPE;
-  if (!acts || (idx_out == nullptr) != (val_out == nullptr)) return CC_ERR_NULL;
-  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
-  if (h > TK_MAX_H || B > (1 << 30)) return CC_ERR_TOO_LARGE;
-  if (((uintptr_t)acts | (uintptr_t)acts_out | (uintptr_t)colsum_part) & 15) return CC_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == CC_BF16)
-    tk_launch<CC_BF16>(acts, ld, B, h, k, acts_out, idx_out, val_out, colsum_part, l0_part, st);
-  else
-    tk_launch<CC_F32>(acts, ld, B, h, k, acts_out, idx_out, val_out, colsum_part, l0_part, st);
+  const int rc = rows_check(ld, B, h, dtype, k >= 1 && k <= h, acts && (idx_out == nullptr) == (val_out == nullptr),
+                            false, {acts, acts_out, colsum_part});
+  if (rc != CC_OK) return rc;
+  CC_BY_DTYPE(tk_launch, dtype, false)(acts, ld, B, h, k, acts_out, idx_out, val_out, colsum_part, l0_part, nullptr, 0,
+                                       nullptr, (hipStream_t)stream);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
 
 int cc_auxk_rows(const void* acts, int64_t ld, int64_t B, int64_t h, int dtype, int k_aux, const int64_t* since_fired,
                  int64_t dead_after, void* aux_out, int32_t* row_count, void* stream) {
-  if (B < 1 || h < 8 || (h & 7) || (ld & 7) || ld < h || k_aux < 1 || k_aux > h) return CC_ERR_SHAPE;
-  if (!acts || !since_fired || !aux_out || aux_out == acts) return CC_ERR_NULL;
-  if (dtype != CC_BF16 && dtype != CC_F32) return CC_ERR_DTYPE;
-  if (h > TK_MAX_H || B > (1 << 30)) return CC_ERR_TOO_LARGE;
-  if ((((uintptr_t)acts | (uintptr_t)aux_out) & 15) || ((uintptr_t)since_fired & 7) || ((uintptr_t)row_count & 3))
-    return CC_ERR_ALIGN;
-  hipStream_t st = (hipStream_t)stream;
-  if (dtype == CC_BF16) ak_launch<CC_BF16>(acts, ld, B, h, k_aux, since_fired, dead_after, aux_out, row_count, st);
-  else ak_launch<CC_F32>(acts, ld, B, h, k_aux, since_fired, dead_after, aux_out, row_count, st);
+  const int rc = rows_check(ld, B, h, dtype, k_aux >= 1 && k_aux <= h, acts && since_fired && aux_out && aux_out != acts,
+                            false, {acts, aux_out}, {row_count}, {since_fired});
+  if (rc != CC_OK) return rc;
+  CC_BY_DTYPE(tk_launch, dtype, true)(acts, ld, B, h, k_aux, aux_out, nullptr, nullptr, nullptr, nullptr, since_fired,
+                                      dead_after, row_count, (hipStream_t)stream);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }

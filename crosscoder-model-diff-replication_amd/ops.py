@@ -62,6 +62,26 @@ def _contig(t, name):
     return t
 
 
+def _rows_ld(t, name):
+    """(rows, row pitch) of a 2-D tensor with contiguous rows"""
+    if t.dim() != 2 or t.stride(1) != 1:
+        raise ValueError(f"{name} must be [rows, width] with contiguous rows")
+    return t.shape[0], t.stride(0) if t.stride(0) >= t.shape[1] else t.shape[1]
+
+
+def _like(t, ref, name, ref_name):
+    """an optional tensor laid out as `ref`"""
+    if t is not None and (t.dtype != ref.dtype or t.shape != ref.shape or t.stride() != ref.stride()
+                          or t.device != ref.device):
+        raise ValueError(f"{name} must have {ref_name}'s dtype, shape, strides and device")
+
+
+def _dense(t, dt, shape, dev, name):
+    """an optional contiguous tensor of one dtype, shape and device"""
+    if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+
+
 def check(rc):
     _lib.check(rc)
 
@@ -731,20 +751,15 @@ def topk_rows(acts, h, k, out=None, idx_out=None, val_out=None, colsum_part=None
     idx_out int32 [B, k] / val_out [B, k] (acts' dtype): the selected pairs by ascending latent, padded with
     (-1, 0); colsum_part fp32 [topk_part_rows(B, h), h] / l0_part fp32 [topk_l0_parts(B, h)]: column-sum partials
     and selected counts of the masked activations."""
-    if acts.dim() != 2 or acts.stride(1) != 1:
-        raise ValueError("acts must be [rows, width] with contiguous rows")
-    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    B, ld = _rows_ld(acts, "acts")
     dev = acts.device
-    if out is not None and (out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride()
-                            or out.device != dev):
-        raise ValueError("out must have acts' dtype, shape, strides and device")
+    _like(out, acts, "out", "acts")
     if (idx_out is None) != (val_out is None):
         raise ValueError("idx_out and val_out go together")
-    for name, t, dt, shape in (("idx_out", idx_out, torch.int32, (B, k)), ("val_out", val_out, acts.dtype, (B, k)),
-                               ("colsum_part", colsum_part, torch.float32, (topk_part_rows(B, h), h)),
-                               ("l0_part", l0_part, torch.float32, (topk_l0_parts(B, h),))):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    _dense(idx_out, torch.int32, (B, k), dev, "idx_out")
+    _dense(val_out, acts.dtype, (B, k), dev, "val_out")
+    _dense(colsum_part, torch.float32, (topk_part_rows(B, h), h), dev, "colsum_part")
+    _dense(l0_part, torch.float32, (topk_l0_parts(B, h),), dev, "l0_part")
     check(lib().cc_topk_rows(_ptr(acts), ld, B, h, dtype_code(acts.dtype), int(k), _ptr(out), _ptr(idx_out),
                              _ptr(val_out), _ptr(colsum_part), _ptr(l0_part), _stream(acts)))
     return out
@@ -764,19 +779,13 @@ def batch_topk_ws_bytes(B, h, dtype, weighted):
 
 
 def _batch_topk_args(acts, h, weight, out, colsum_part, l0_part, row_count):
-    if acts.dim() != 2 or acts.stride(1) != 1:
-        raise ValueError("acts must be [rows, width] with contiguous rows")
-    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    B, ld = _rows_ld(acts, "acts")
     dev = acts.device
-    if out is not None and (out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride()
-                            or out.device != dev):
-        raise ValueError("out must have acts' dtype, shape, strides and device")
-    for name, t, dt, shape in (("weight", weight, torch.float32, (h,)),
-                               ("colsum_part", colsum_part, torch.float32, (batch_topk_part_rows(B, h), h)),
-                               ("l0_part", l0_part, torch.float32, (batch_topk_l0_parts(B, h),)),
-                               ("row_count", row_count, torch.int32, (B,))):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape {shape} on {dev}")
+    _like(out, acts, "out", "acts")
+    _dense(weight, torch.float32, (h,), dev, "weight")
+    _dense(colsum_part, torch.float32, (batch_topk_part_rows(B, h), h), dev, "colsum_part")
+    _dense(l0_part, torch.float32, (batch_topk_l0_parts(B, h),), dev, "l0_part")
+    _dense(row_count, torch.int32, (B,), dev, "row_count")
     return B, ld
 
 
@@ -797,9 +806,7 @@ def batch_topk(acts, h, n_keep, weight=None, out=None, colsum_part=None, l0_part
     if out is None and info is None and row_count is None:
         raise ValueError("at least one of out, info and row_count is needed")
     dev = acts.device
-    if info is not None and (info.dtype != torch.int32 or tuple(info.shape) != (4,) or info.device != dev
-                             or not info.is_contiguous()):
-        raise ValueError(f"info must be a contiguous int32 tensor of shape (4,) on {dev}")
+    _dense(info, torch.int32, (4,), dev, "info")
     if threshold is not None and (threshold.dtype != torch.float32 or threshold.numel() != 1
                                   or threshold.device != dev or not 0 <= beta < 1):
         raise ValueError(f"threshold must be an fp32 tensor of one element on {dev}, beta a float in [0, 1)")
@@ -829,12 +836,6 @@ def threshold_mask(acts, h, theta, weight=None, out=None, colsum_part=None, l0_p
 
 
 # ---------------------------------------------------------------- the AuxK dead-latent loss
-def _rows_ld(t, name):
-    if t.dim() != 2 or t.stride(1) != 1:
-        raise ValueError(f"{name} must be [rows, width] with contiguous rows")
-    return t.shape[0], t.stride(0) if t.stride(0) >= t.shape[1] else t.shape[1]
-
-
 def auxk_rows(acts, h, k_aux, since_fired, dead_after, out, row_count=None):
     """Each row of acts [B, ld >= h], first h columns, reduced to its k_aux largest positive values among the dead
     latents only (since_fired [>= h] int64 on the device; dead: since_fired >= dead_after), into `out` (acts' dtype,
@@ -842,16 +843,13 @@ def auxk_rows(acts, h, k_aux, since_fired, dead_after, out, row_count=None):
     every row's selected count."""
     B, ld = _rows_ld(acts, "acts")
     dev = acts.device
-    if out.dtype != acts.dtype or out.shape != acts.shape or out.stride() != acts.stride() or out.device != dev:
-        raise ValueError("out must have acts' dtype, shape, strides and device")
+    _like(out, acts, "out", "acts")
     if out.data_ptr() == acts.data_ptr():
         raise ValueError("out must not be acts")
     if since_fired.dtype != torch.int64 or since_fired.device != dev or since_fired.dim() != 1 \
             or since_fired.numel() < h or not since_fired.is_contiguous():
         raise ValueError(f"since_fired must be a contiguous int64 tensor of at least {h} elements on {dev}")
-    if row_count is not None and (row_count.dtype != torch.int32 or tuple(row_count.shape) != (B,)
-                                  or row_count.device != dev or not row_count.is_contiguous()):
-        raise ValueError(f"row_count must be a contiguous int32 tensor of shape ({B},) on {dev}")
+    _dense(row_count, torch.int32, (B,), dev, "row_count")
     check(lib().cc_auxk_rows(_ptr(acts), ld, B, h, dtype_code(acts.dtype), int(k_aux), _ptr(since_fired),
                              int(dead_after), _ptr(out), _ptr(row_count), _stream(acts)))
     return out
@@ -864,10 +862,9 @@ def dead_update(colsum_acts, since_fired, h_real, B, dead_after, count_out, was_
     count (cc_dead_update)."""
     h = colsum_acts.numel()
     dev = colsum_acts.device
-    for name, t, dt in (("colsum_acts", colsum_acts, torch.float32), ("since_fired", since_fired, torch.int64),
-                        ("was_dead", was_dead, torch.uint8)):
-        if t is not None and (t.dtype != dt or tuple(t.shape) != (h,) or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous {dt} tensor of shape ({h},) on {dev}")
+    _dense(colsum_acts, torch.float32, (h,), dev, "colsum_acts")
+    _dense(since_fired, torch.int64, (h,), dev, "since_fired")
+    _dense(was_dead, torch.uint8, (h,), dev, "was_dead")
     if count_out.dtype != torch.int32 or count_out.numel() != 1 or count_out.device != dev:
         raise ValueError(f"count_out must be an int32 tensor of one element on {dev}")
     check(lib().cc_dead_update(_ptr(colsum_acts), _ptr(since_fired), h, int(h_real), int(B), int(dead_after),
@@ -903,8 +900,7 @@ def add_rows(dst, src):
     """dst = dtype(float(dst) + float(src)) for two [rows, cols] views of the same dtype and row stride
     (cc_add_rows)."""
     rows, ld = _rows_ld(dst, "dst")
-    if src.dtype != dst.dtype or src.shape != dst.shape or src.stride() != dst.stride() or src.device != dst.device:
-        raise ValueError("src must have dst's dtype, shape, strides and device")
+    _like(src, dst, "src", "dst")
     check(lib().cc_add_rows(_ptr(dst), _ptr(src), rows, dst.shape[1], ld, dtype_code(dst.dtype), _stream(dst)))
 
 
@@ -924,14 +920,10 @@ def _jumprelu_args(a, h, theta, same, slabs):
     B, ld = _rows_ld(a, "acts")
     dev = a.device
     for name, t in same:
-        if t is not None and (t.dtype != a.dtype or t.shape != a.shape or t.stride() != a.stride() or t.device != dev):
-            raise ValueError(f"{name} must have acts' dtype, shape, strides and device")
-    if theta.dtype != torch.float32 or tuple(theta.shape) != (h,) or theta.device != dev or not theta.is_contiguous():
-        raise ValueError(f"theta must be a contiguous fp32 tensor of shape ({h},) on {dev}")
+        _like(t, a, name, "acts")
+    _dense(theta, torch.float32, (h,), dev, "theta")
     for name, t in slabs:
-        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (jumprelu_part_rows(B, h), h)
-                              or t.device != dev or not t.is_contiguous()):
-            raise ValueError(f"{name} must be a contiguous fp32 tensor of shape ({jumprelu_part_rows(B, h)}, {h}) on {dev}")
+        _dense(t, torch.float32, (jumprelu_part_rows(B, h), h), dev, name)
     return B, ld
 
 
@@ -944,9 +936,7 @@ def jumprelu_mask(acts, h, theta, eps, out, gate=None, colsum_part=None, l0_part
     B, ld = _jumprelu_args(acts, h, theta, (("out", out), ("gate", gate)), (("colsum_part", colsum_part),))
     if gate is not None and gate.data_ptr() == acts.data_ptr():
         raise ValueError("gate must not be acts")
-    if l0_part is not None and (l0_part.dtype != torch.float32 or tuple(l0_part.shape) != (jumprelu_l0_parts(B, h),)
-                                or l0_part.device != acts.device or not l0_part.is_contiguous()):
-        raise ValueError(f"l0_part must be a contiguous fp32 tensor of shape ({jumprelu_l0_parts(B, h)},)")
+    _dense(l0_part, torch.float32, (jumprelu_l0_parts(B, h),), acts.device, "l0_part")
     check(lib().cc_jumprelu_mask(_ptr(acts), ld, B, h, dtype_code(acts.dtype), _ptr(theta), float(eps), _ptr(out),
                                  _ptr(gate), _ptr(colsum_part), _ptr(l0_part), _stream(acts)))
     return out
