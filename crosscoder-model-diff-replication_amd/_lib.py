@@ -152,6 +152,7 @@ SIGNATURES = {
     "cc_jumprelu_l0_parts": (_i64, [_i64, _i64]),
     "cc_jumprelu_mask": (_i, [_p, _i64, _i64, _i64, _i, _p, _f, _p, _p, _p, _p, _p]),
     "cc_jumprelu_bwd": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _f, _f, _p, _p, _p]),
+    "cc_decode_pairs": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i64, _p, _p]),
 }
 
 _lib = None

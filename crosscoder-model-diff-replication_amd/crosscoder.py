@@ -401,6 +401,11 @@ class CrossCoder(nn.Module):
         activations of relu(x W_enc + b_enc) (ties: the smaller latent) in ascending latent index, padded with
         (0, -1) where fewer are positive -- the compact form of a wide dictionary's activations.  Framework
         extension; serves any crosscoder (k defaults to cfg["k"]); indices refer to the dict_size latents."""
+        return self._encode_compact(x, k, own=False)
+
+    def _encode_compact(self, x, k, own, use_threshold=None):
+        """encode_topk (own=False: the k largest of relu(pre)) / encode_pairs (own=True: of the crosscoder's own
+        activation): ENCODE_ROWS rows at a time through one activation buffer, cc_topk_rows writing only the pairs."""
         k = self.k if k is None else k
         if isinstance(k, bool) or not isinstance(k, int) or not 1 <= k <= self.d_hidden:
             raise ValueError(f"k must be an int in 1..dict_size ({self.d_hidden}), got {k!r}")
@@ -414,8 +419,63 @@ class CrossCoder(nn.Module):
             r1 = min(rows, r0 + self.ENCODE_ROWS)
             acts = buf[:r1 - r0]
             ops.encode_fwd(self._flat_x(x[r0:r1]), a.W_enc_hk, a.b_enc, acts, True)
+            if own:
+                self.activate_(acts, use_threshold)
             ops.topk_rows(acts, self._hp, k, idx_out=idx[r0:r1], val_out=vals[r0:r1])
         return vals, idx
+
+    def encode_pairs(self, x, k=None, use_threshold=None):
+        """x [rows, n_models, d_model] -> (values [rows, k], indices [rows, k] int32): the crosscoder's OWN activations
+        -- what encode(x, use_threshold=use_threshold) gives: ReLU, TopK, the BatchTopK selection / threshold mask,
+        JumpReLU -- in encode_topk's compact form (ascending latent index, padded at the end with (0, -1)).  Exact where
+        k >= the row's number of non-zero activations; a row with more keeps its k largest.  k defaults to cfg["k"]
+        and is required for a crosscoder without one.  ENCODE_ROWS rows at a time: a BatchTopK crosscoder without a
+        threshold selects among the rows of each such slice.  Framework extension; decode_pairs / pairs_sq_err take
+        the pairs back to the residual stream without the dense [rows, dict_size] matrix."""
+        return self._encode_compact(x, k, own=True, use_threshold=use_threshold)
+
+    def _pairs(self, values, indices):
+        """(values, indices) as cc_decode_pairs reads them: [rows, k] of the crosscoder's dtype and int32, contiguous
+        (int64 indices are converted; one beyond int32 stays out of range)."""
+        if values.dim() != 2 or indices.shape != values.shape or values.shape[1] < 1:
+            raise ValueError(f"expected values and indices of one shape [rows, k >= 1], got {tuple(values.shape)} and "
+                             f"{tuple(indices.shape)}")
+        if indices.dtype not in (torch.int32, torch.int64):
+            raise ValueError(f"indices must be int32 or int64, got {indices.dtype}")
+        if indices.dtype == torch.int64:
+            indices = indices.clamp(min=-1, max=self.d_hidden).to(torch.int32)
+        return values.to(self.dtype).contiguous(), indices.contiguous()
+
+    def decode_pairs(self, values, indices):
+        """(values, indices) [rows, k] as encode_pairs / encode_topk give them -> [rows, n_models, d_model] incl. b_dec:
+        the sparse counterpart of decode (cc_decode_pairs: k decoder rows gathered per token, an fp32 sum in slot
+        order rounded once).  A slot whose index is outside [0, dict_size) -- the -1 padding -- adds nothing."""
+        a = self.arena()
+        a.wait_pending()
+        vals, idx = self._pairs(values, indices)
+        B = vals.shape[0]
+        out = torch.empty(B, self.n_models * self._dp, dtype=self.dtype, device=vals.device)
+        if B:
+            ops.decode_pairs(vals, idx, a.W_dec_hk, a.b_dec_flat, self.n_models, self._dp, h=self.d_hidden, recon=out)
+        out = out.view(B, self.n_models, self._dp)
+        return out[:, :, :self.cfg["d_in"]].contiguous() if self._dp != self.cfg["d_in"] else out
+
+    def pairs_sq_err(self, values, indices, x):
+        """fp32 [rows, n_models]: per row and model, sum_d (decode_pairs(values, indices) - x)^2 of the rounded
+        reconstruction (crosscoder.py:104's squared difference), from the same kernel pass: the reconstruction is
+        never stored."""
+        a = self.arena()
+        a.wait_pending()
+        vals, idx = self._pairs(values, indices)
+        B = vals.shape[0]
+        self._check_x(x)
+        if x.shape[0] != B:
+            raise ValueError(f"x has {x.shape[0]} rows, the pairs {B}")
+        sq = torch.empty(B, self.n_models, dtype=torch.float32, device=vals.device)
+        if B:
+            ops.decode_pairs(vals, idx, a.W_dec_hk, a.b_dec_flat, self.n_models, self._dp, h=self.d_hidden,
+                             x=self._flat_x(x), sq_err=sq)
+        return sq
 
     def decode(self, acts):
         """acts [batch, d_hidden] -> [batch, n_models, d_model] incl. b_dec (crosscoder.py:82-89)."""

@@ -765,6 +765,57 @@ def topk_rows(acts, h, k, out=None, idx_out=None, val_out=None, colsum_part=None
     return out
 
 
+# ---------------------------------------------------------------- sparse decode from pairs (the pairs' consumer)
+def decode_pairs(val, idx, W_dec, b_dec, n, d, h=None, recon=None, x=None, sq_err=None):
+    """The decode of k (value, latent) pairs per row, topk_rows' val_out / idx_out (cc_decode_pairs): per row r and
+    column c an fp32 fma chain  b_dec[c] + sum_s val[r, s] * W_dec[idx[r, s], c]  over the slots in order, rounded
+    once to the dtype.  A slot whose index is outside [0, h) adds nothing (h defaults to W_dec's rows).
+    val [B, k] (bf16 / fp32) and idx [B, k] int32, contiguous; W_dec [>= h, >= n * d], b_dec [n * d]; recon and x
+    [B, >= n * d] of val's dtype (W_dec, recon and x may be column slices of wider matrices: their row pitch is
+    kept); sq_err fp32 [B, n]: per row and model, the squared error of the rounded reconstruction against x.
+    Without x: writes (and returns) recon, allocated if not given.  With x: writes sq_err (allocated if not given),
+    and recon only if given.  -> (recon or None, sq_err or None)."""
+    if val.dim() != 2 or idx.dim() != 2 or val.shape != idx.shape or val.shape[0] < 1 or val.shape[1] < 1:
+        raise ValueError(f"val and idx must both be [rows >= 1, k >= 1], got {tuple(val.shape)} and {tuple(idx.shape)}")
+    if val.dtype not in _DT:
+        raise ValueError(f"val must be bf16 or fp32, got {val.dtype}")
+    if idx.dtype != torch.int32:
+        raise ValueError(f"idx must be int32, got {idx.dtype}")
+    if not val.is_contiguous() or not idx.is_contiguous():
+        raise ValueError("val and idx must be contiguous")
+    for name, v in (("n", n), ("d", d)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if d % 8:
+        raise ValueError(f"d must be a multiple of 8, got {d}")
+    B, k = val.shape
+    K, dt, dev = n * d, val.dtype, val.device
+    if W_dec.dim() != 2 or W_dec.shape[1] < K:
+        raise ValueError(f"W_dec must be [h, >= {K}], got {tuple(W_dec.shape)}")
+    h = W_dec.shape[0] if h is None else h
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
+        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
+    _dense(b_dec, dt, (K,), dev, "b_dec")
+    if sq_err is not None and x is None:
+        raise ValueError("sq_err needs x")
+    _dense(sq_err, torch.float32, (B, n), dev, "sq_err")
+    for name, t in (("W_dec", W_dec), ("recon", recon), ("x", x), ("idx", idx)):
+        if t is not None and (t.device != dev or (name != "idx" and t.dtype != dt)):
+            raise ValueError(f"{name} must be on {dev}" + ("" if name == "idx" else f" with dtype {dt}"))
+    for name, t in (("recon", recon), ("x", x)):
+        if t is not None and (t.dim() != 2 or t.shape[0] != B):
+            raise ValueError(f"{name} must be [{B}, >= {K}], got {tuple(t.shape)}")
+    pw, ldw = _pitched(W_dec, K, "W_dec")
+    if x is None and recon is None:
+        recon = torch.empty(B, K, dtype=dt, device=dev)
+    if x is not None and sq_err is None:
+        sq_err = torch.empty(B, n, dtype=torch.float32, device=dev)
+    (pr, ldr), (px, ldx) = ((None, 0) if t is None else _pitched(t, K, name) for name, t in (("recon", recon), ("x", x)))
+    check(lib().cc_decode_pairs(_ptr(val), _ptr(idx), B, k, pw, ldw, h, _ptr(b_dec), n, d, dtype_code(dt), pr, ldr,
+                                px, ldx, _ptr(sq_err), _stream(val)))
+    return recon, sq_err
+
+
 # ---------------------------------------------------------------- BatchTopK (one selection over the whole batch)
 def batch_topk_part_rows(B, h):
     return int(lib().cc_batch_topk_part_rows(B, h))

@@ -712,6 +712,29 @@ int cc_jumprelu_mask(const void* acts, int64_t ld, int64_t B, int64_t h, int dty
 int cc_jumprelu_bwd(void* g_pre, const void* gate, int64_t ld, int64_t B, int64_t h, int dtype, const float* theta,
                     float eps, float l0_scale, float* gpre_colsum_part, float* thr_part, void* stream);
 
+/* ---- Sparse decode from (value, latent) pairs: the consumer of cc_topk_rows' idx_out / val_out (CrossCoder.decode_pairs,
+ * pairs_sq_err, LatentAblation).  A whole-row gather of W_dec plus one fp32 fma chain per output element; no [B][h]
+ * activation matrix is formed.  K = n * d.
+ *   val [B][k] (dtype), idx [B][k] (int32), both dense;  W_dec [h][ldw], b_dec [K], x [B][ldx], recon [B][ldr] (dtype);
+ *   sq_err [B][n] (fp32).
+ * For row r, column c:  acc = float(b_dec[c]);  for slots s = 0 .. k-1 in that order, if 0 <= idx[r][s] < h:
+ *   acc = fmaf(float(val[r][s]), float(W_dec[idx[r][s]][c]), acc).
+ * A slot whose index is outside [0, h) (the -1 padding or anything else; one unsigned compare) adds nothing and its
+ * W_dec row is not read; duplicate indices add twice; a row with no valid slot gives b_dec's bits.
+ *   recon[r][c] = dtype(acc), one round-to-nearest-even.  (bf16: a product of two bf16 values is exact in fp32, so
+ *   the chain is a plain fp32 multiply-add loop.)
+ *   sq_err[r][m] = sum over c in [m d, (m+1) d) of (float(dtype(acc)) - float(x[r][c]))^2 in fp32, in an order fixed
+ *   by (K, d) alone (lanes, waves and LDS in lane order; no float atomics): two calls give the same bits, and the
+ *   same bits whether or not recon is written.
+ * recon and (x, sq_err) are each optional (NULL), at least one given; x and sq_err go together; recon != x.
+ * Errors, checked in this order before any launch: CC_ERR_SHAPE (B, k, h or n < 1, d < 8 or d % 8 != 0, ldw < K, a
+ * given recon's ldr < K, a given x's ldx < K), CC_ERR_NULL (val, idx, W_dec or b_dec missing, neither output, one of
+ * x / sq_err without the other, recon == x), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h or K > 2^31 - 1, k > 2^17),
+ * CC_ERR_ALIGN (16 bytes: W_dec, b_dec, x, recon and their row pitches; 4 bytes: idx, sq_err; val: its element). */
+int cc_decode_pairs(const void* val, const int32_t* idx, int64_t B, int k, const void* W_dec, int64_t ldw, int64_t h,
+                    const void* b_dec, int64_t n, int64_t d, int dtype, void* recon, int64_t ldr, const void* x,
+                    int64_t ldx, float* sq_err, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
