@@ -587,11 +587,7 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_kernel(const GemmArgs args) {
 //       dispatch wave -- into clock[0] / clock[1] and counts the launch in clock[2], so the host reads the clock
 //       the chip held over the roofline launches (bench.py `effective_sclk_ghz`).
 constexpr int CC_WGRAD_CLOCK_WORDS = 8;  // (floats: the 4 uint64 clock words after the tile sums)
-struct WgradTail {
-  RedSeg red[2];
-  int red_blocks[2];
-  ClipArgs clip;
-  unsigned* counter;
+struct WgradTail : TailArgs {  // (the tail's own arguments first, as make_grad_tail_args fills them)
   float* tile_sum;  // [2 * nb0]: the per-tile squared sums, dW_dec's tiles first
   uint64_t* clock;  // [4] after tile_sum's tile sums: shader ticks, 100 MHz ticks, launches, (reserved)
 };
@@ -1511,106 +1507,102 @@ int cc_wgrad_enc(const void* g_pre, const void* x, void* grad_W_enc, float* sq_p
   return launch_dt<EPI_WGENC, false, false>(dtype, a, (hipStream_t)stream);
 }
 
-int cc_wgrad_both_t(const void* actsT, const void* g_reconT, const void* W_dec, const float* inv_norms,
-                    const float* colsum_acts, float l1_scale, void* grad_W_dec, float* sq_dec, const void* g_preT,
-                    const void* xT, void* grad_W_enc, float* sq_enc, int64_t B, int64_t h, int64_t n, int64_t d,
-                    int dtype, void* stream) {
-  GemmArgs a0, a1;
-  int rc = wgrad_dec_args(a0, actsT, g_reconT, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, B, h, n,
-                          d, dtype, true);
-  if (rc) return rc;
-  rc = wgrad_enc_args(a1, g_preT, xT, grad_W_enc, sq_enc, B, h, n * d, dtype, true);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (!use_pp(a0.N, true, true, dtype)) {
-    rc = launch_dt<EPI_WGDEC, true, true>(dtype, a0, st);
-    return rc ? rc : launch_dt<EPI_WGENC, true, true>(dtype, a1, st);
-  }
+}  // extern "C"
+
+// G4 + G5 in one call: the operands wgrad_dec_args / wgrad_enc_args consume, batch-major or (the _t entries)
+// transposed
+struct WgradOps {
+  const void *acts, *g_recon, *W_dec;
+  const float *inv_norms, *colsum_acts;
+  float l1_scale;
+  void* grad_W_dec;
+  float* sq_dec;
+  const void *g_pre, *x;
+  void* grad_W_enc;
+  float* sq_enc;
+  int64_t B, h, n, d;
+  int dtype;
+};
+// ... and the grad tail their launch carries: the tail's own inputs, the per-tile squared sums' scratch and the
+// dynamic tile order's counters (nullptr: static order)
+struct WgradTailIn {
+  GradTailIn tail;
+  float* tile_sum;
+  uint32_t* tile_ctr;
+};
+
+static int wgrad_both_args(GemmArgs& a0, GemmArgs& a1, const WgradOps& o, bool tr) {
+  const int rc = wgrad_dec_args(a0, o.acts, o.g_recon, o.W_dec, o.inv_norms, o.colsum_acts, o.l1_scale, o.grad_W_dec,
+                                o.sq_dec, o.B, o.h, o.n, o.d, o.dtype, tr);
+  return rc ? rc : wgrad_enc_args(a1, o.g_pre, o.x, o.grad_W_enc, o.sq_enc, o.B, o.h, o.n * o.d, o.dtype, tr);
+}
+
+// The dual launch's tile grid (both GEMMs have the same) and, for the transposed forms in the test library, the
+// launch-form hooks; returns the launch's workgroups.
+static int wgrad_dual_grid(GemmArgs& a0, GemmArgs& a1, bool tr, hipStream_t st) {
   a0.nbm = a1.nbm = (a0.M + BM - 1) / BM;
   a0.nbn = a1.nbn = (a0.N + 255) / 256;
 #ifdef CC_DEBUG_HOOKS
-  debug_wave_sync(a0, st);
-  debug_epi_store(a0);
-  debug_epi_store(a1, (int64_t)a0.nbm * a0.nbn);
+  if (tr) {
+    debug_wave_sync(a0, st);
+    debug_epi_store(a0);
+    debug_epi_store(a1, (int64_t)a0.nbm * a0.nbn);
+  }
 #endif
-  hipLaunchKernelGGL((gemm_pp_dual_kernel<true, true, EPI_WGDEC, EPI_WGENC>), dim3(pp_grid(2 * a0.nbm * a0.nbn)), dim3(NTHR),
-                     0, st, a0, a1);
+  return pp_grid(2 * a0.nbm * a0.nbn);
+}
+
+// cc_wgrad_both (TR false) / cc_wgrad_both_t (TR true)
+template <bool TR>
+static int wgrad_both(const WgradOps& o, hipStream_t st) {
+  GemmArgs a0, a1;
+  int rc = wgrad_both_args(a0, a1, o, TR);
+  if (rc) return rc;
+  if (!use_pp(a0.N, TR, TR, o.dtype)) {
+    rc = launch_dt<EPI_WGDEC, TR, TR>(o.dtype, a0, st);
+    return rc ? rc : launch_dt<EPI_WGENC, TR, TR>(o.dtype, a1, st);
+  }
+  const int grid = wgrad_dual_grid(a0, a1, TR, st);
+  hipLaunchKernelGGL((gemm_pp_dual_kernel<TR, TR, EPI_WGDEC, EPI_WGENC>), dim3(grid), dim3(NTHR), 0, st, a0, a1);
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
 
-// (step_kernels.hip, library-internal: cc_grad_tail / cc_grad_tail_sums with the step's abort word)
-extern "C" int cc_grad_tail_sums_abort(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc,
-                                       float* sq_b_enc, const float* loss_colpart, int64_t R_dec, int64_t K,
-                                       void* g_b_dec, float* sq_b_dec, int dtype, const float* sq, const int64_t* off,
-                                       int nparams, int zero_mask, float* out, uint32_t* counter,
-                                       const uint32_t* abort, void* stream);
-extern "C" int cc_grad_tail_abort(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc, float* sq_b_enc,
-                                  const float* loss_colpart, int64_t R_dec, int64_t K, void* g_b_dec, float* sq_b_dec,
-                                  int dtype, const float* sq, const int64_t* off, int nparams, float max_norm,
-                                  int emulate_bf16, float* clip_out, uint32_t* counter, const uint32_t* abort,
-                                  void* stream);
-
-static int wgrad_both_tail(const void* actsT, const void* g_reconT, const void* W_dec, const float* inv_norms,
-                           const float* colsum_acts, float l1_scale, void* grad_W_dec, float* sq_dec, const void* g_preT,
-                           const void* xT, void* grad_W_enc, float* sq_enc, int64_t B, int64_t h, int64_t n, int64_t d,
-                           const float* gpre_colpart, int64_t R_enc, void* g_b_enc, float* sq_b_enc,
-                           const float* loss_colpart, int64_t R_dec, void* g_b_dec, float* sq_b_dec, const float* sq,
-                           const int64_t* off, int nparams, float max_norm, int emulate_bf16, int sums_only,
-                           int zero_mask, float* out, uint32_t* counter, float* tile_sum, uint32_t* tile_ctr,
-                           const uint32_t* abort, int dtype, void* stream) {
-  const int64_t K = n * d;
-  if (!gpre_colpart || !g_b_enc || !sq_b_enc || !loss_colpart || !g_b_dec || !sq_b_dec || !sq || !off || !out ||
-      !counter || !tile_sum || !sq_dec || !sq_enc)  // (the clip's W_dec / W_enc sums come from sq_dec / sq_enc's tiles)
-    return CC_ERR_NULL;
-  if (R_enc <= 0 || R_dec <= 0) return CC_ERR_SHAPE;
-  if (nparams != 4) return CC_ERR_SHAPE;  // W_enc, W_dec, b_enc, b_dec: the segments of sq
-  GemmArgs a0, a1;
-  int rc = wgrad_dec_args(a0, actsT, g_reconT, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, B, h, n,
-                          d, dtype, true);
-  if (rc) return rc;
-  rc = wgrad_enc_args(a1, g_preT, xT, grad_W_enc, sq_enc, B, h, K, dtype, true);
-  if (rc) return rc;
-  if (dtype != CC_BF16 || !use_pp(a0.N, true, true, dtype)) {  // the two GEMMs, then the stand-alone tail
-    rc = cc_wgrad_both_t(actsT, g_reconT, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, g_preT, xT,
-                         grad_W_enc, sq_enc, B, h, n, d, dtype, stream);
-    if (rc) return rc;
-    if (sums_only)
-      return cc_grad_tail_sums_abort(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec,
-                                     sq_b_dec, dtype, sq, off, nparams, zero_mask, out, counter, abort, stream);
-    return cc_grad_tail_abort(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec, sq_b_dec,
-                              dtype, sq, off, nparams, max_norm, emulate_bf16, out, counter, abort, stream);
-  }
-  a0.nbm = a1.nbm = (a0.M + BM - 1) / BM;
-  a0.nbn = a1.nbn = (a0.N + 255) / 256;
+// cc_wgrad_both_clip_t / cc_wgrad_both_sums_t
+static int wgrad_both_tail(const WgradOps& o, const WgradTailIn& t, hipStream_t st) {
+  // (the clip's W_dec / W_enc sums come from sq_dec / sq_enc's tiles)
+  if (!t.tile_sum || !o.sq_dec || !o.sq_enc) return CC_ERR_NULL;
   WgradTail tl = {};
-  tl.red[0] = {gpre_colpart, (int)R_enc, (int)h, h, 1.f, nullptr, g_b_enc, sq_b_enc, nullptr, nullptr};
-  tl.red[1] = {loss_colpart, (int)R_dec, (int)K, K, 1.f, nullptr, g_b_dec, sq_b_dec, nullptr, nullptr};
-  tl.red_blocks[0] = (int)((h + RED_COLS - 1) / RED_COLS);
-  tl.red_blocks[1] = (int)((K + RED_COLS - 1) / RED_COLS);
-  tl.clip.sq = sq;
-  for (int i = 0; i <= nparams; ++i) tl.clip.off[i] = off[i];
-  tl.clip.nparams = nparams;
-  tl.clip.max_norm = max_norm;
-  tl.clip.emulate_bf16 = emulate_bf16;
-  tl.clip.out = out;
-  tl.clip.sums_only = sums_only;
-  tl.clip.zero_mask = zero_mask;
-  tl.clip.abort = abort;
-  tl.counter = counter;
-  tl.tile_sum = tile_sum;
-  tl.clock = (uint64_t*)(tile_sum + 2 * a0.nbm * a0.nbn);  // (2 * nb0 is even: 8-byte aligned)
-  a0.tile_ctr = tile_ctr;
-#ifdef CC_DEBUG_HOOKS
-  debug_wave_sync(a0, (hipStream_t)stream);
-  debug_epi_store(a0);
-  debug_epi_store(a1, (int64_t)a0.nbm * a0.nbn);
-#endif
-  const int grid = pp_grid(2 * a0.nbm * a0.nbn);
-  hipLaunchKernelGGL((gemm_pp_dual_tail_kernel<true, true, EPI_WGDEC, EPI_WGENC>), dim3(grid), dim3(NTHR), 0,
-                     (hipStream_t)stream, a0, a1, tl);
+  int rc = make_grad_tail_args(tl, t.tail);
+  if (rc) return rc;
+  if (t.tail.nparams != 4) return CC_ERR_SHAPE;  // W_enc, W_dec, b_enc, b_dec: the segments of sq
+  GemmArgs a0, a1;
+  if ((rc = wgrad_both_args(a0, a1, o, true))) return rc;
+  if (o.dtype != CC_BF16 || !use_pp(a0.N, true, true, o.dtype)) {  // the two GEMMs, then the stand-alone tail
+    rc = wgrad_both<true>(o, st);
+    return rc ? rc : launch_grad_tail(tl, o.dtype, st);
+  }
+  a0.tile_ctr = t.tile_ctr;
+  const int grid = wgrad_dual_grid(a0, a1, true, st);
+  tl.tile_sum = t.tile_sum;
+  tl.clock = (uint64_t*)(t.tile_sum + 2 * a0.nbm * a0.nbn);  // (2 * nb0 is even: 8-byte aligned)
+  hipLaunchKernelGGL((gemm_pp_dual_tail_kernel<true, true, EPI_WGDEC, EPI_WGENC>), dim3(grid), dim3(NTHR), 0, st, a0,
+                     a1, tl);
   CC_LAUNCH_CHECK();
   return CC_OK;
+}
+
+extern "C" {
+
+int cc_wgrad_both_t(const void* actsT, const void* g_reconT, const void* W_dec, const float* inv_norms,
+                    const float* colsum_acts, float l1_scale, void* grad_W_dec, float* sq_dec, const void* g_preT,
+                    const void* xT, void* grad_W_enc, float* sq_enc, int64_t B, int64_t h, int64_t n, int64_t d,
+                    int dtype, void* stream) {
+  const WgradOps o = {.acts = actsT, .g_recon = g_reconT, .W_dec = W_dec, .inv_norms = inv_norms,
+                      .colsum_acts = colsum_acts, .l1_scale = l1_scale, .grad_W_dec = grad_W_dec, .sq_dec = sq_dec,
+                      .g_pre = g_preT, .x = xT, .grad_W_enc = grad_W_enc, .sq_enc = sq_enc, .B = B, .h = h, .n = n,
+                      .d = d, .dtype = dtype};
+  return wgrad_both<true>(o, (hipStream_t)stream);
 }
 
 int cc_wgrad_both_clip_t(const void* actsT, const void* g_reconT, const void* W_dec, const float* inv_norms,
@@ -1621,10 +1613,18 @@ int cc_wgrad_both_clip_t(const void* actsT, const void* g_reconT, const void* W_
                          const int64_t* off, int nparams, float max_norm, int emulate_bf16, float* clip_out,
                          uint32_t* counter, float* tile_sum, uint32_t* tile_ctr, const uint32_t* abort_flag, int dtype,
                          void* stream) {
-  return wgrad_both_tail(actsT, g_reconT, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, g_preT, xT,
-                         grad_W_enc, sq_enc, B, h, n, d, gpre_colpart, R_enc, g_b_enc, sq_b_enc, loss_colpart, R_dec,
-                         g_b_dec, sq_b_dec, sq, off, nparams, max_norm, emulate_bf16, 0, 0, clip_out, counter, tile_sum,
-                         tile_ctr, abort_flag, dtype, stream);
+  const WgradOps o = {.acts = actsT, .g_recon = g_reconT, .W_dec = W_dec, .inv_norms = inv_norms,
+                      .colsum_acts = colsum_acts, .l1_scale = l1_scale, .grad_W_dec = grad_W_dec, .sq_dec = sq_dec,
+                      .g_pre = g_preT, .x = xT, .grad_W_enc = grad_W_enc, .sq_enc = sq_enc, .B = B, .h = h, .n = n,
+                      .d = d, .dtype = dtype};
+  const WgradTailIn t = {
+      .tail = {.gpre_colpart = gpre_colpart, .R_enc = R_enc, .h = h, .g_b_enc = g_b_enc, .sq_b_enc = sq_b_enc,
+               .loss_colpart = loss_colpart, .R_dec = R_dec, .K = n * d, .g_b_dec = g_b_dec, .sq_b_dec = sq_b_dec,
+               .sq = sq, .off = off, .nparams = nparams,
+               .max_norm = max_norm, .emulate_bf16 = emulate_bf16, .out = clip_out, .counter = counter,
+               .abort = abort_flag},
+      .tile_sum = tile_sum, .tile_ctr = tile_ctr};
+  return wgrad_both_tail(o, t, (hipStream_t)stream);
 }
 
 int cc_wgrad_both_sums_t(const void* actsT, const void* g_reconT, const void* W_dec, const float* inv_norms,
@@ -1634,34 +1634,28 @@ int cc_wgrad_both_sums_t(const void* actsT, const void* g_reconT, const void* W_
                          const float* loss_colpart, int64_t R_dec, void* g_b_dec, float* sq_b_dec, const float* sq,
                          const int64_t* off, int nparams, int zero_mask, float* out, uint32_t* counter, float* tile_sum,
                          uint32_t* tile_ctr, const uint32_t* abort, int dtype, void* stream) {
-  return wgrad_both_tail(actsT, g_reconT, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, g_preT, xT,
-                         grad_W_enc, sq_enc, B, h, n, d, gpre_colpart, R_enc, g_b_enc, sq_b_enc, loss_colpart, R_dec,
-                         g_b_dec, sq_b_dec, sq, off, nparams, 0.f, 0, 1, zero_mask, out, counter, tile_sum, tile_ctr,
-                         abort, dtype, stream);
+  const WgradOps o = {.acts = actsT, .g_recon = g_reconT, .W_dec = W_dec, .inv_norms = inv_norms,
+                      .colsum_acts = colsum_acts, .l1_scale = l1_scale, .grad_W_dec = grad_W_dec, .sq_dec = sq_dec,
+                      .g_pre = g_preT, .x = xT, .grad_W_enc = grad_W_enc, .sq_enc = sq_enc, .B = B, .h = h, .n = n,
+                      .d = d, .dtype = dtype};
+  const WgradTailIn t = {
+      .tail = {.gpre_colpart = gpre_colpart, .R_enc = R_enc, .h = h, .g_b_enc = g_b_enc, .sq_b_enc = sq_b_enc,
+               .loss_colpart = loss_colpart, .R_dec = R_dec, .K = n * d, .g_b_dec = g_b_dec, .sq_b_dec = sq_b_dec,
+               .sq = sq, .off = off, .nparams = nparams,
+               .sums_only = 1, .zero_mask = zero_mask, .out = out, .counter = counter, .abort = abort},
+      .tile_sum = tile_sum, .tile_ctr = tile_ctr};
+  return wgrad_both_tail(o, t, (hipStream_t)stream);
 }
 
 int cc_wgrad_both(const void* acts, const void* g_recon, const void* W_dec, const float* inv_norms,
                   const float* colsum_acts, float l1_scale, void* grad_W_dec, float* sq_dec, const void* g_pre,
                   const void* x, void* grad_W_enc, float* sq_enc, int64_t B, int64_t h, int64_t n, int64_t d,
                   int dtype, void* stream) {
-  GemmArgs a0, a1;
-  int rc = wgrad_dec_args(a0, acts, g_recon, W_dec, inv_norms, colsum_acts, l1_scale, grad_W_dec, sq_dec, B, h, n, d,
-                          dtype);
-  if (rc) return rc;
-  rc = wgrad_enc_args(a1, g_pre, x, grad_W_enc, sq_enc, B, h, n * d, dtype);
-  if (rc) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  if (!use_pp(a0.N, false, false, dtype)) {
-    rc = launch_dt<EPI_WGDEC, false, false>(dtype, a0, st);
-    return rc ? rc : launch_dt<EPI_WGENC, false, false>(dtype, a1, st);
-  }
-  a0.nbm = a1.nbm = (a0.M + BM - 1) / BM;
-  a0.nbn = a1.nbn = (a0.N + 255) / 256;
-  hipLaunchKernelGGL((gemm_pp_dual_kernel<false, false, EPI_WGDEC, EPI_WGENC>), dim3(pp_grid(2 * a0.nbm * a0.nbn)),
-                     dim3(NTHR),
-                     0, st, a0, a1);
-  CC_LAUNCH_CHECK();
-  return CC_OK;
+  const WgradOps o = {.acts = acts, .g_recon = g_recon, .W_dec = W_dec, .inv_norms = inv_norms,
+                      .colsum_acts = colsum_acts, .l1_scale = l1_scale, .grad_W_dec = grad_W_dec, .sq_dec = sq_dec,
+                      .g_pre = g_pre, .x = x, .grad_W_enc = grad_W_enc, .sq_enc = sq_enc, .B = B, .h = h, .n = n,
+                      .d = d, .dtype = dtype};
+  return wgrad_both<false>(o, (hipStream_t)stream);
 }
 
 }  // extern "C"

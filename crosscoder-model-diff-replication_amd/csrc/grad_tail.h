@@ -1,6 +1,9 @@
 // Gradient-tail building blocks shared by the stand-alone tail kernels (step_kernels.hip) and the
 // weight-gradient GEMM that runs the grad tail in its own launch (gemm.hip): fixed-order column
-// reductions of partial slabs and the clip_grad_norm_ finaliser.  Included inside namespace cc.
+// reductions of partial slabs and the clip_grad_norm_ finaliser (device side); the tail's kernel
+// arguments TailArgs, the one host builder that checks and fills them for every launch form
+// (make_grad_tail_args, as make_loss_tail_args for the loss tail) and the stand-alone launcher's
+// declaration (host side).  Included inside namespace cc.
 #pragma once
 
 // ---------------------------------------------------------------------------------------
@@ -179,3 +182,64 @@ CC_DEV void clip_finish(const ClipArgs& a, const double* s, double (*red)[NT / 6
   }
 }
 
+// ---------------------------------------------------------------------------------------
+// The grad tail's kernel arguments: two column reductions (RedSeg: b_enc.grad, b_dec.grad column sums + their sq
+// partials) in 256-thread groups, then the last workgroup to arrive (counter) runs the clip finaliser or the segment
+// sums over the partials the whole grid wrote.  tail_kernel (step_kernels.hip) takes them as they are; the G4G5
+// launch that carries the tail appends its own words (gemm.hip WgradTail).
+struct TailArgs {
+  RedSeg red[2];
+  int red_blocks[2];  // 256-thread groups per reduction (0: unused)
+  ClipArgs clip;
+  unsigned* counter;
+};
+
+// What a caller hands the grad tail, whichever launch runs it (cc_grad_tail, cc_grad_tail_sums, the fused G4G5
+// entries and their fallback): the two slabs with their bias gradients and sq partials, the squared-sum segments sq /
+// off / nparams, and either the clip's scalars or sums_only + zero_mask (ClipArgs).  abort: the step's abort word
+// (ClipArgs::abort; nullptr: none).
+struct GradTailIn {
+  const float* gpre_colpart;  // [R_enc][h] -> g_b_enc, sq_b_enc
+  int64_t R_enc, h;
+  void* g_b_enc;
+  float* sq_b_enc;
+  const float* loss_colpart;  // [R_dec][K] -> g_b_dec, sq_b_dec
+  int64_t R_dec, K;
+  void* g_b_dec;
+  float* sq_b_dec;
+  const float* sq;
+  const int64_t* off;
+  int nparams;
+  float max_norm;
+  int emulate_bf16;
+  int sums_only, zero_mask;
+  float* out;
+  uint32_t* counter;
+  const uint32_t* abort;
+};
+// The only copy of the tail's argument checks (NULL, then the shapes, then nparams) and of the field fill.
+static inline int make_grad_tail_args(TailArgs& a, const GradTailIn& in) {
+  if (!in.gpre_colpart || !in.g_b_enc || !in.sq_b_enc || !in.loss_colpart || !in.g_b_dec || !in.sq_b_dec || !in.sq ||
+      !in.off || !in.out || !in.counter)
+    return CC_ERR_NULL;
+  if (in.R_enc <= 0 || in.R_dec <= 0 || in.h <= 0 || in.K <= 0) return CC_ERR_SHAPE;
+  if (in.nparams <= 0 || in.nparams > 8) return CC_ERR_SHAPE;
+  a = TailArgs{};
+  a.red[0] = {in.gpre_colpart, (int)in.R_enc, (int)in.h, in.h, 1.f, nullptr, in.g_b_enc, in.sq_b_enc, nullptr, nullptr};
+  a.red[1] = {in.loss_colpart, (int)in.R_dec, (int)in.K, in.K, 1.f, nullptr, in.g_b_dec, in.sq_b_dec, nullptr, nullptr};
+  a.red_blocks[0] = (int)((in.h + RED_COLS - 1) / RED_COLS);
+  a.red_blocks[1] = (int)((in.K + RED_COLS - 1) / RED_COLS);
+  a.clip.sq = in.sq;
+  for (int i = 0; i <= in.nparams; ++i) a.clip.off[i] = in.off[i];
+  a.clip.nparams = in.nparams;
+  a.clip.max_norm = in.max_norm;
+  a.clip.emulate_bf16 = in.emulate_bf16;
+  a.clip.out = in.out;
+  a.clip.sums_only = in.sums_only;
+  a.clip.zero_mask = in.zero_mask;
+  a.clip.abort = in.abort;
+  a.counter = in.counter;
+  return CC_OK;
+}
+// The stand-alone launch of tail_kernel<dtype> (step_kernels.hip; library-internal)
+int launch_grad_tail(const TailArgs& a, int dtype, hipStream_t stream);

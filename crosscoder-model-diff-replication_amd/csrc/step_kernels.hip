@@ -374,16 +374,10 @@ CC_DEV bool arrive_last(unsigned* counter, int* last) {
   return *last;
 }
 
-// Fused grad tail: one launch of 1024-thread blocks = 4 independent 256-thread groups, each running one
-// block of a column reduction (RedSeg: b_enc.grad, b_dec.grad column sums + their sq partials) -- the same
+// Fused grad tail (TailArgs, grad_tail.h): one launch of 1024-thread blocks = 4 independent 256-thread groups, each
+// running one block of a column reduction (RedSeg: b_enc.grad, b_dec.grad column sums + their sq partials) -- the same
 // two phases as the stand-alone kernel, so the same bits -- then the last block to finish runs clip_body
 // (or the segment sums) over the partials the whole grid wrote.  Saves the finaliser's launch per step.
-struct TailArgs {
-  RedSeg red[2];
-  int red_blocks[2];  // 256-thread groups per reduction (0: unused)
-  ClipArgs clip;
-  unsigned* counter;
-};
 template <int DT>
 __global__ __launch_bounds__(SCAL_THREADS) void tail_kernel(const TailArgs a) {
   __shared__ float red[4][4][RED_COLS];
@@ -1634,74 +1628,39 @@ static int adam_launch(const AdamArgs& a, int64_t max_blocks, int dtype, hipStre
   return CC_OK;
 }
 
-extern "C" {
-
-
-static int grad_tail(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc, float* sq_b_enc,
-                     const float* loss_colpart, int64_t R_dec, int64_t K, void* g_b_dec, float* sq_b_dec, int dtype,
-                     const float* sq, const int64_t* off, int nparams, float max_norm, int emulate_bf16,
-                     int sums_only, int zero_mask, float* out, uint32_t* counter, void* stream,
-                     const uint32_t* abort = nullptr) {
-  if (!gpre_colpart || !g_b_enc || !sq_b_enc || !loss_colpart || !g_b_dec || !sq_b_dec || !sq || !off || !out ||
-      !counter)
-    return CC_ERR_NULL;
-  if (R_enc <= 0 || R_dec <= 0 || h <= 0 || K <= 0) return CC_ERR_SHAPE;
-  if (nparams <= 0 || nparams > 8) return CC_ERR_SHAPE;
-  TailArgs a = {};
-  a.red[0] = {gpre_colpart, (int)R_enc, (int)h, h, 1.f, nullptr, g_b_enc, sq_b_enc, nullptr, nullptr};
-  a.red[1] = {loss_colpart, (int)R_dec, (int)K, K, 1.f, nullptr, g_b_dec, sq_b_dec, nullptr, nullptr};
-  a.red_blocks[0] = (int)((h + RED_COLS - 1) / RED_COLS);
-  a.red_blocks[1] = (int)((K + RED_COLS - 1) / RED_COLS);
-  a.clip.sq = sq;
-  for (int i = 0; i <= nparams; ++i) a.clip.off[i] = off[i];
-  a.clip.nparams = nparams;
-  a.clip.max_norm = max_norm;
-  a.clip.emulate_bf16 = emulate_bf16;
-  a.clip.out = out;
-  a.clip.sums_only = sums_only;
-  a.clip.zero_mask = zero_mask;
-  a.clip.abort = abort;
-  a.counter = counter;
+int cc::launch_grad_tail(const TailArgs& a, int dtype, hipStream_t st) {
   dim3 grid((unsigned)((a.red_blocks[0] + a.red_blocks[1] + 3) / 4));
-  hipStream_t st = (hipStream_t)stream;
   DISPATCH_DT(dtype, hipLaunchKernelGGL((tail_kernel<DT_>), grid, dim3(SCAL_THREADS), 0, st, a));
   CC_LAUNCH_CHECK();
   return CC_OK;
 }
 
+extern "C" {
+
 int cc_grad_tail(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc, float* sq_b_enc,
                  const float* loss_colpart, int64_t R_dec, int64_t K, void* g_b_dec, float* sq_b_dec, int dtype,
                  const float* sq, const int64_t* off, int nparams, float max_norm, int emulate_bf16, float* clip_out,
                  uint32_t* counter, void* stream) {
-  return grad_tail(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec, sq_b_dec, dtype, sq,
-                   off, nparams, max_norm, emulate_bf16, 0, 0, clip_out, counter, stream);
-}
-
-// cc_grad_tail with the step's abort word (ClipArgs::abort): the fused G4G5 entry's fallback (library-internal)
-int cc_grad_tail_abort(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc, float* sq_b_enc,
-                       const float* loss_colpart, int64_t R_dec, int64_t K, void* g_b_dec, float* sq_b_dec, int dtype,
-                       const float* sq, const int64_t* off, int nparams, float max_norm, int emulate_bf16,
-                       float* clip_out, uint32_t* counter, const uint32_t* abort, void* stream) {
-  return grad_tail(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec, sq_b_dec, dtype, sq,
-                   off, nparams, max_norm, emulate_bf16, 0, 0, clip_out, counter, stream, abort);
-}
-
-// (library-internal: cc_grad_tail_sums with the step's abort word -- the latent-sharded step's fallback form)
-extern "C" int cc_grad_tail_sums_abort(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc,
-                                       float* sq_b_enc, const float* loss_colpart, int64_t R_dec, int64_t K,
-                                       void* g_b_dec, float* sq_b_dec, int dtype, const float* sq, const int64_t* off,
-                                       int nparams, int zero_mask, float* out, uint32_t* counter,
-                                       const uint32_t* abort, void* stream) {
-  return grad_tail(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec, sq_b_dec, dtype, sq,
-                   off, nparams, 0.f, 0, 1, zero_mask, out, counter, stream, abort);
+  const GradTailIn in = {.gpre_colpart = gpre_colpart, .R_enc = R_enc, .h = h, .g_b_enc = g_b_enc, .sq_b_enc = sq_b_enc,
+                         .loss_colpart = loss_colpart, .R_dec = R_dec, .K = K, .g_b_dec = g_b_dec, .sq_b_dec = sq_b_dec,
+                         .sq = sq, .off = off, .nparams = nparams, .max_norm = max_norm, .emulate_bf16 = emulate_bf16,
+                         .out = clip_out, .counter = counter};
+  TailArgs a;
+  const int rc = make_grad_tail_args(a, in);
+  return rc ? rc : launch_grad_tail(a, dtype, (hipStream_t)stream);
 }
 
 int cc_grad_tail_sums(const float* gpre_colpart, int64_t R_enc, int64_t h, void* g_b_enc, float* sq_b_enc,
                       const float* loss_colpart, int64_t R_dec, int64_t K, void* g_b_dec, float* sq_b_dec, int dtype,
                       const float* sq, const int64_t* off, int nparams, int zero_mask, float* out, uint32_t* counter,
                       void* stream) {
-  return grad_tail(gpre_colpart, R_enc, h, g_b_enc, sq_b_enc, loss_colpart, R_dec, K, g_b_dec, sq_b_dec, dtype, sq,
-                   off, nparams, 0.f, 0, 1, zero_mask, out, counter, stream);
+  const GradTailIn in = {.gpre_colpart = gpre_colpart, .R_enc = R_enc, .h = h, .g_b_enc = g_b_enc, .sq_b_enc = sq_b_enc,
+                         .loss_colpart = loss_colpart, .R_dec = R_dec, .K = K, .g_b_dec = g_b_dec, .sq_b_dec = sq_b_dec,
+                         .sq = sq, .off = off, .nparams = nparams, .sums_only = 1, .zero_mask = zero_mask, .out = out,
+                         .counter = counter};
+  TailArgs a;
+  const int rc = make_grad_tail_args(a, in);
+  return rc ? rc : launch_grad_tail(a, dtype, (hipStream_t)stream);
 }
 
 int cc_loss_tail(const float* colsum_acts, const float* tn, int64_t h, float* l1_part, const float* row_part,

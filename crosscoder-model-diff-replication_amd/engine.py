@@ -680,6 +680,36 @@ def dacts_rows(ws, P, l1_coeff, r0, r1, l1_grad_weight=1.0):
                           colsum_part=ws.gpre_colpart[c0:c1])
 
 
+def _wgrad_operands(ws, P, G, l1_scale, tr):
+    """ops.wgrad_both*'s weight-gradient operands (through n, d) for this workspace: the transposed batch operands
+    (tr) or the batch-major ones"""
+    batch = (ws.acts_t, ws.g_recon_t, ws.g_pre_t, ws.x_t) if tr else (ws.acts, ws.g_recon, ws.g_pre, ws.x)
+    return (*batch[:2], P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale, G.W_dec_hk, ws.sq_slice(1), *batch[2:],
+            G.W_enc_hk, ws.sq_slice(0), ws.n, ws.d)
+
+
+def _bias_operands(ws, G, gpre_colpart):
+    """the grad tail's bias operands: the g_pre column-partial slab -> b_enc.grad, the loss's -> b_dec.grad"""
+    return gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3)
+
+
+def _bias_grads(ws, G, gpre_colpart, offsets, clip=None, sums_out=None, zero_mask=0, emulate=None):
+    """The backward's end after G4 / G5: the bias gradients (+ their sq partials) from the two column-partial slabs,
+    with -- sums_out -- the per-parameter squared sums or -- clip -- clip_grad_norm_'s coefficient (then ws.clip_ready)
+    in the same launch; neither: the two reductions alone.  offsets: the segments of ws.sq the sums / the clip cover;
+    emulate: the clip's emulate_bf16 (default: torch's roundings for a bf16 crosscoder's four parameters)."""
+    bias = _bias_operands(ws, G, gpre_colpart)
+    if sums_out is not None:
+        ops.grad_tail_sums(*bias, ws.sq, offsets, sums_out, ws.tail_ctr[1:2], zero_mask=zero_mask)
+    elif clip is not None:
+        ops.grad_tail(*bias, ws.sq, offsets, clip, ws.dtype == torch.bfloat16 if emulate is None else emulate,
+                      ws.clip_out, ws.tail_ctr[1:2])
+        ws.clip_ready = True
+    else:
+        ops.reduce_rows(gpre_colpart, gpre_colpart.shape[0], ws.h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
+        ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, ws.K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+
+
 def backward(ws, P, G, l1_coeff, l1_grad_weight=1.0, dacts_done=False, clip=None, sums_out=None, zero_mask=0,
              tail_done=None, l0_coeff=0.0, theta_grad=None):
     """Gradients of l2 + l1_coeff * l1 into the grads Arena G (+ squared-sum partials).
@@ -693,53 +723,33 @@ def backward(ws, P, G, l1_coeff, l1_grad_weight=1.0, dacts_done=False, clip=None
         if dacts_done or sums_out is not None or l1_grad_weight != 1.0:
             raise ValueError("the JumpReLU step has no sliced or sharded form")
         return backward_jumprelu(ws, P, G, l1_coeff, l0_coeff, theta_grad, clip, tail_done)
-    B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
-    l1_scale = float(l1_coeff) * l1_grad_weight / B
+    l1_scale = float(l1_coeff) * l1_grad_weight / ws.B
     # (a deferred decoder-half Adam launch of the last step reads the clip coefficient this launch rewrites)
     P.wait_pending()
     if not dacts_done:
-        dacts_rows(ws, P, l1_coeff, 0, B, l1_grad_weight)
+        dacts_rows(ws, P, l1_coeff, 0, ws.B, l1_grad_weight)
     if tail_done is not None:
         tail_done.wait(torch.cuda.current_stream(ws.x.device))
+    wgrad = _wgrad_operands(ws, P, G, l1_scale, ws.tr)
+    abort_ptr = ws.wait_err.device_ptr if ws.wait_err is not None else None
     if sums_out is not None and ws.tr:
         # G4 + G5 and the grad tail's per-parameter squared sums (for the all-reduce) in one launch
         with _span("G4G5_wgrad"):
-            ops.wgrad_both_sums_t(ws.acts_t, ws.g_recon_t, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale,
-                                  G.W_dec_hk, ws.sq_slice(1), ws.g_pre_t, ws.x_t, G.W_enc_hk, ws.sq_slice(0), n, d,
-                                  ws.gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat,
-                                  ws.sq_slice(3), ws.sq, ws.sq_off, sums_out, ws.tail_ctr[1:2], ws.tile_sum,
-                                  zero_mask=zero_mask, tile_ctr=_tile_ctr(ws, 2),
-                                  abort_ptr=ws.wait_err.device_ptr if ws.wait_err is not None else None)
+            ops.wgrad_both_sums_t(*wgrad, *_bias_operands(ws, G, ws.gpre_colpart), ws.sq, ws.sq_off, sums_out,
+                                  ws.tail_ctr[1:2], ws.tile_sum, zero_mask=zero_mask, tile_ctr=_tile_ctr(ws, 2),
+                                  abort_ptr=abort_ptr)
         return
     if clip is not None and ws.tr:
         # G4 + G5 and the grad tail (bias sums + clip coefficient) in one launch
         with _span("G4G5_wgrad"):
-            ops.wgrad_both_clip_t(ws.acts_t, ws.g_recon_t, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale,
-                                  G.W_dec_hk, ws.sq_slice(1), ws.g_pre_t, ws.x_t, G.W_enc_hk, ws.sq_slice(0), n, d,
-                                  ws.gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat,
-                                  ws.sq_slice(3), ws.sq, ws.sq_off, clip, ws.dtype == torch.bfloat16, ws.clip_out,
-                                  ws.tail_ctr[1:2], ws.tile_sum, tile_ctr=_tile_ctr(ws, 2),
-                                  abort_ptr=ws.wait_err.device_ptr if ws.wait_err is not None else None)
+            ops.wgrad_both_clip_t(*wgrad, *_bias_operands(ws, G, ws.gpre_colpart), ws.sq, ws.sq_off, clip,
+                                  ws.dtype == torch.bfloat16, ws.clip_out, ws.tail_ctr[1:2], ws.tile_sum,
+                                  tile_ctr=_tile_ctr(ws, 2), abort_ptr=abort_ptr)
         ws.clip_ready = True
         return
     with _span("G4G5_wgrad"):
-        if ws.tr:
-            ops.wgrad_both_t(ws.acts_t, ws.g_recon_t, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale,
-                             G.W_dec_hk, ws.sq_slice(1), ws.g_pre_t, ws.x_t, G.W_enc_hk, ws.sq_slice(0), n, d)
-        else:
-            ops.wgrad_both(ws.acts, ws.g_recon, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale, G.W_dec_hk,
-                           ws.sq_slice(1), ws.g_pre, ws.x, G.W_enc_hk, ws.sq_slice(0), n, d)
-    if sums_out is not None:
-        ops.grad_tail_sums(ws.gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3),
-                           ws.sq, ws.sq_off, sums_out, ws.tail_ctr[1:2], zero_mask=zero_mask)
-        return
-    if clip is not None:
-        ops.grad_tail(ws.gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3), ws.sq,
-                      ws.sq_off, clip, ws.dtype == torch.bfloat16, ws.clip_out, ws.tail_ctr[1:2])
-        ws.clip_ready = True
-        return
-    ops.reduce_rows(ws.gpre_colpart, ws.gpre_colpart.shape[0], h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
-    ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+        (ops.wgrad_both_t if ws.tr else ops.wgrad_both)(*wgrad)
+    _bias_grads(ws, G, ws.gpre_colpart, ws.sq_off, clip, sums_out, zero_mask)
 
 
 def backward_jumprelu(ws, P, G, l1_coeff, l0_coeff=0.0, theta_grad=None, clip=None, tail_done=None):
@@ -750,7 +760,7 @@ def backward_jumprelu(ws, P, G, l1_coeff, l0_coeff=0.0, theta_grad=None, clip=No
     then G4G5 and the grad tail as always, the tail over the recomputed column partials and -- theta_grad given --
     five parameters.  theta_grad None (get_losses' autograd, which serves the four reference parameters): the pass
     only restores the straight-through g_pre, and the clip is over four."""
-    B, n, d, h = ws.B, ws.n, ws.d, ws.h
+    B, h = ws.B, ws.h
     l1_scale = float(l1_coeff) / B
     P.wait_pending()
     dacts_rows(ws, P, l1_coeff, 0, B)
@@ -763,16 +773,9 @@ def backward_jumprelu(ws, P, G, l1_coeff, l0_coeff=0.0, theta_grad=None, clip=No
     if tail_done is not None:
         tail_done.wait(torch.cuda.current_stream(ws.x.device))
     with _span("G4G5_wgrad"):
-        ops.wgrad_both(ws.acts, ws.g_recon, P.W_dec_hk, ws.inv_norms, ws.colsum_acts, l1_scale, G.W_dec_hk,
-                       ws.sq_slice(1), ws.g_pre, ws.x, G.W_enc_hk, ws.sq_slice(0), n, d)
+        ops.wgrad_both(*_wgrad_operands(ws, P, G, l1_scale, False))
     off = ws.sq_off if theta_grad is not None else ws.sq_off[:5]
-    if clip is not None:
-        ops.grad_tail(ws.jr_gpre_colpart, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3),
-                      ws.sq, off, clip, clip_emulation(ws, len(off) - 1), ws.clip_out, ws.tail_ctr[1:2])
-        ws.clip_ready = True
-        return
-    ops.reduce_rows(ws.jr_gpre_colpart, ws.jr_gpre_colpart.shape[0], h, out_t=G.b_enc, sq_part=ws.sq_slice(2))
-    ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, ws.K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+    _bias_grads(ws, G, ws.jr_gpre_colpart, off, clip, emulate=clip_emulation(ws, len(off) - 1))
 
 
 def clip_emulation(ws, nparams=4):
@@ -822,9 +825,7 @@ def backward_auxk(ws, P, G, l1_coeff, clip):
                       ws.sq_slice(1), n, d)
     with _span("G5_wgrad_enc"):
         ops.wgrad_enc(ws.g_pre, ws.x, G.W_enc_hk, ws.sq_slice(0))
-    ops.grad_tail(ws.gpre_colpart_full, G.b_enc, ws.sq_slice(2), loss_colpart(ws), G.b_dec_flat, ws.sq_slice(3), ws.sq,
-                  ws.sq_off, clip, ws.dtype == torch.bfloat16, ws.clip_out, ws.tail_ctr[1:2])
-    ws.clip_ready = True
+    _bias_grads(ws, G, ws.gpre_colpart_full, ws.sq_off, clip)
 
 
 # workgroups of the decoder-half Adam that runs beside the next step's G1 (128 / 192 / 384 / 512 measured

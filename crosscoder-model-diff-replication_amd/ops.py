@@ -54,6 +54,29 @@ def _ctr(t):
     return _ptr(t)
 
 
+def _offsets(offsets):
+    """(the int64 array of a squared-sum segment list's offsets, its number of segments)"""
+    return (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets]), len(offsets) - 1
+
+
+def _wgrad_operands(acts, g_recon, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec, g_pre, x, grad_enc, sq_enc,
+                    n, d, tr):
+    """cc_wgrad_both*'s first 16 arguments: the 12 weight-gradient operands, then B, h, n, d (tr: the batch operands are
+    transposed, acts [h][B])"""
+    B, h = acts.shape[::-1] if tr else acts.shape
+    return (_ptr(acts), _ptr(g_recon), _ptr(W_dec_hk), _ptr(norms), _ptr(colsum_acts), l1_scale, _ptr(grad_dec),
+            _ptr(sq_dec), _ptr(g_pre), _ptr(x), _ptr(grad_enc), _ptr(sq_enc), B, h, n, d)
+
+
+def _bias_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, cols):
+    """The grad tail's bias operands in the C ABI's order: per slab its pointer, rows (and, cols: the stand-alone
+    entries, columns), the bias gradient and its sq partials"""
+    out = []
+    for slab, g, sq in ((gpre_colpart, g_b_enc, sq_b_enc), (loss_colpart, g_b_dec, sq_b_dec)):
+        out += [_ptr(slab), *slab.shape[:2 if cols else 1], _ptr(g), _ptr(sq)]
+    return out
+
+
 def _contig(t, name):
     if not t.is_contiguous():
         raise ValueError(f"{name} must be contiguous")
@@ -325,27 +348,25 @@ def loss_tail(colsum_acts, tn, l1_part, row_part, l0_part, n_l0, ev, ev_a, ev_b,
 def grad_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, sq, offsets, max_norm, emulate_bf16,
               out, counter):
     """The two bias-gradient reduce_rows (+ sq partials) + clip_finalize as one launch (same bits)."""
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
-    check(lib().cc_grad_tail(_ptr(gpre_colpart), gpre_colpart.shape[0], gpre_colpart.shape[1], _ptr(g_b_enc),
-                             _ptr(sq_b_enc), _ptr(loss_colpart), loss_colpart.shape[0], loss_colpart.shape[1],
-                             _ptr(g_b_dec), _ptr(sq_b_dec), dtype_code(g_b_enc.dtype), _ptr(sq), arr, len(offsets) - 1,
-                             max_norm, int(emulate_bf16), _ptr(out), _ptr(counter), _stream(sq)))
+    arr, nparams = _offsets(offsets)
+    check(lib().cc_grad_tail(*_bias_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, True),
+                             dtype_code(g_b_enc.dtype), _ptr(sq), arr, nparams, max_norm, int(emulate_bf16), _ptr(out),
+                             _ptr(counter), _stream(sq)))
 
 
 def grad_tail_sums(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, sq, offsets, out, counter,
                    zero_mask=0):
     """The two bias-gradient reduce_rows (+ sq partials) + segment_sums as one launch (same bits)."""
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
-    check(lib().cc_grad_tail_sums(_ptr(gpre_colpart), gpre_colpart.shape[0], gpre_colpart.shape[1], _ptr(g_b_enc),
-                                  _ptr(sq_b_enc), _ptr(loss_colpart), loss_colpart.shape[0], loss_colpart.shape[1],
-                                  _ptr(g_b_dec), _ptr(sq_b_dec), dtype_code(g_b_enc.dtype), _ptr(sq), arr,
-                                  len(offsets) - 1, int(zero_mask), _ptr(out), _ptr(counter), _stream(sq)))
+    arr, nparams = _offsets(offsets)
+    check(lib().cc_grad_tail_sums(*_bias_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, True),
+                                  dtype_code(g_b_enc.dtype), _ptr(sq), arr, nparams, int(zero_mask), _ptr(out),
+                                  _ptr(counter), _stream(sq)))
 
 
 def segment_sums(sq, offsets, out, zero_mask=0):
     """out[p] = sum(sq[offsets[p]:offsets[p+1]]) (0 where bit p of zero_mask is set)."""
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
-    check(lib().cc_segment_sums(_ptr(sq), arr, len(offsets) - 1, int(zero_mask), _ptr(out), _stream(sq)))
+    arr, nparams = _offsets(offsets)
+    check(lib().cc_segment_sums(_ptr(sq), arr, nparams, int(zero_mask), _ptr(out), _stream(sq)))
 
 
 def dacts_bwd(g_recon, W_dec_hk, acts, tn, l1_scale, g_pre, colsum_part=None):
@@ -462,19 +483,17 @@ def wgrad_enc(g_pre, x, grad, sq_part):
 def wgrad_both(acts, g_recon, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec, g_pre, x, grad_enc, sq_enc,
                n, d):
     """wgrad_dec + wgrad_enc (same results), one launch where the ping-pong GEMM serves both."""
-    B, h = acts.shape
-    check(lib().cc_wgrad_both(_ptr(acts), _ptr(g_recon), _ptr(W_dec_hk), _ptr(norms), _ptr(colsum_acts), l1_scale,
-                              _ptr(grad_dec), _ptr(sq_dec), _ptr(g_pre), _ptr(x), _ptr(grad_enc), _ptr(sq_enc), B, h,
-                              n, d, dtype_code(acts.dtype), _stream(acts)))
+    check(lib().cc_wgrad_both(*_wgrad_operands(acts, g_recon, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec,
+                                               g_pre, x, grad_enc, sq_enc, n, d, False),
+                              dtype_code(acts.dtype), _stream(acts)))
 
 
 def wgrad_both_t(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec, g_preT, xT, grad_enc,
                  sq_enc, n, d):
     """wgrad_both from transposed batch operands (actsT / g_preT [h][B], g_reconT / xT [n*d][B]); same results."""
-    h, B = actsT.shape
-    check(lib().cc_wgrad_both_t(_ptr(actsT), _ptr(g_reconT), _ptr(W_dec_hk), _ptr(norms), _ptr(colsum_acts), l1_scale,
-                                _ptr(grad_dec), _ptr(sq_dec), _ptr(g_preT), _ptr(xT), _ptr(grad_enc), _ptr(sq_enc), B,
-                                h, n, d, dtype_code(actsT.dtype), _stream(actsT)))
+    check(lib().cc_wgrad_both_t(*_wgrad_operands(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec,
+                                                 sq_dec, g_preT, xT, grad_enc, sq_enc, n, d, True),
+                                dtype_code(actsT.dtype), _stream(actsT)))
 
 
 def wgrad_tile_sums(h, K):
@@ -506,15 +525,14 @@ def wgrad_both_clip_t(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, g
     """wgrad_both_t + grad_tail in one launch (the bias sums before the GEMM tiles, the clip coefficient
     in the last workgroup); same outputs.  abort_ptr: device address of the step's abort word (when set, out[0] is
     written as CLIP_ABORTED and the Adam launches reading it apply nothing)."""
-    h, B = actsT.shape
-    _check_tile_sum(tile_sum, h, n * d)
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
+    _check_tile_sum(tile_sum, actsT.shape[0], n * d)
+    arr, nparams = _offsets(offsets)
     check(lib().cc_wgrad_both_clip_t(
-        _ptr(actsT), _ptr(g_reconT), _ptr(W_dec_hk), _ptr(norms), _ptr(colsum_acts), l1_scale, _ptr(grad_dec),
-        _ptr(sq_dec), _ptr(g_preT), _ptr(xT), _ptr(grad_enc), _ptr(sq_enc), B, h, n, d, _ptr(gpre_colpart),
-        gpre_colpart.shape[0], _ptr(g_b_enc), _ptr(sq_b_enc), _ptr(loss_colpart), loss_colpart.shape[0], _ptr(g_b_dec),
-        _ptr(sq_b_dec), _ptr(sq), arr, len(offsets) - 1, max_norm, int(emulate_bf16), _ptr(out), _ptr(counter),
-        _ptr(tile_sum), _ctr(tile_ctr), _vptr(abort_ptr), dtype_code(actsT.dtype), _stream(actsT)))
+        *_wgrad_operands(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec, g_preT, xT,
+                         grad_enc, sq_enc, n, d, True),
+        *_bias_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, False), _ptr(sq), arr, nparams,
+        max_norm, int(emulate_bf16), _ptr(out), _ptr(counter), _ptr(tile_sum), _ctr(tile_ctr), _vptr(abort_ptr),
+        dtype_code(actsT.dtype), _stream(actsT)))
 
 
 CLIP_ABORTED = -1.0  # clip_out[0] of a step whose update was not applied (include/crosscoder_hip.h)
@@ -525,21 +543,19 @@ def wgrad_both_sums_t(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, g
                       counter, tile_sum, zero_mask=0, tile_ctr=None, abort_ptr=None):
     """wgrad_both_t + grad_tail_sums in one launch (the latent-sharded step); same outputs.  abort_ptr: device address
     of the step's abort word (when set, every out[p] is -inf: the all-reduced sums abort every rank's Adam)."""
-    h, B = actsT.shape
-    _check_tile_sum(tile_sum, h, n * d)
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
+    _check_tile_sum(tile_sum, actsT.shape[0], n * d)
+    arr, nparams = _offsets(offsets)
     check(lib().cc_wgrad_both_sums_t(
-        _ptr(actsT), _ptr(g_reconT), _ptr(W_dec_hk), _ptr(norms), _ptr(colsum_acts), l1_scale, _ptr(grad_dec),
-        _ptr(sq_dec), _ptr(g_preT), _ptr(xT), _ptr(grad_enc), _ptr(sq_enc), B, h, n, d, _ptr(gpre_colpart),
-        gpre_colpart.shape[0], _ptr(g_b_enc), _ptr(sq_b_enc), _ptr(loss_colpart), loss_colpart.shape[0], _ptr(g_b_dec),
-        _ptr(sq_b_dec), _ptr(sq), arr, len(offsets) - 1, int(zero_mask), _ptr(out), _ptr(counter), _ptr(tile_sum),
-        _ctr(tile_ctr), _vptr(abort_ptr), dtype_code(actsT.dtype), _stream(actsT)))
+        *_wgrad_operands(actsT, g_reconT, W_dec_hk, norms, colsum_acts, l1_scale, grad_dec, sq_dec, g_preT, xT,
+                         grad_enc, sq_enc, n, d, True),
+        *_bias_tail(gpre_colpart, g_b_enc, sq_b_enc, loss_colpart, g_b_dec, sq_b_dec, False), _ptr(sq), arr, nparams,
+        int(zero_mask), _ptr(out), _ptr(counter), _ptr(tile_sum), _ctr(tile_ctr), _vptr(abort_ptr),
+        dtype_code(actsT.dtype), _stream(actsT)))
 
 
 def clip_finalize(sq, offsets, max_norm, emulate_bf16, out):
-    arr = (ctypes.c_int64 * len(offsets))(*[int(o) for o in offsets])
-    check(lib().cc_clip_finalize(_ptr(sq), arr, len(offsets) - 1, max_norm, int(emulate_bf16), _ptr(out),
-                                 _stream(sq)))
+    arr, nparams = _offsets(offsets)
+    check(lib().cc_clip_finalize(_ptr(sq), arr, nparams, max_norm, int(emulate_bf16), _ptr(out), _stream(sq)))
 
 
 def adam_step(p, g, m, v, coef, lr, beta1, beta2, eps, step, max_blocks=0):

@@ -107,6 +107,38 @@ def test_argument_validation_without_gpu():
     assert lib.cc_decode_loss_t(*bad) == 3                            # d % 64
 
 
+def test_grad_tail_forms_share_their_argument_checks():
+    """Every launch form of the grad tail (cc_grad_tail_sums, and the G4G5 launches that carry it: cc_wgrad_both_clip_t /
+    cc_wgrad_both_sums_t) returns cc_grad_tail's codes in cc_grad_tail's order -- NULL, then the shapes, then nparams --
+    before anything is launched; the fused forms take exactly four parameters and need their tile-sum scratch."""
+    lib = _lib.load()
+    null, fake = ctypes.c_void_p(0), ctypes.c_void_p(1 << 20)
+    off = (ctypes.c_int64 * 10)(*range(10))
+    NULL, SHAPE = 1, 3
+
+    def sums(slab=fake, R_enc=16, nparams=4):
+        return lib.cc_grad_tail_sums(slab, R_enc, 256, fake, fake, fake, 128, 64, fake, fake, 1, fake, off, nparams, 0,
+                                     fake, fake, null)
+
+    assert sums(slab=null) == NULL
+    assert sums(R_enc=0) == SHAPE
+    assert sums(nparams=9) == SHAPE
+    assert sums(slab=null, R_enc=0, nparams=9) == NULL      # NULL first
+    for name, extra in (("cc_wgrad_both_clip_t", [ctypes.c_float(1.0), 1]), ("cc_wgrad_both_sums_t", [0])):
+        def fused(slab=fake, R_enc=2, nparams=4, tile_sum=fake):
+            # B = 64, h = 256, n = 2, d = 32 (bf16); both slabs, both bias gradients and their sq partials; sq, off
+            return getattr(lib, name)(fake, fake, fake, fake, fake, ctypes.c_float(0.03), fake, fake, fake, fake, fake,
+                                      fake, 64, 256, 2, 32, slab, R_enc, fake, fake, fake, 2, fake, fake, fake, off,
+                                      nparams, *extra, fake, fake, tile_sum, null, null, 1, null)
+
+        assert fused(slab=null) == NULL, name
+        assert fused(tile_sum=null) == NULL, name
+        assert fused(R_enc=0) == SHAPE, name
+        assert fused(nparams=9) == SHAPE, name
+        assert fused(nparams=5) == SHAPE, name              # W_enc, W_dec, b_enc, b_dec: exactly the four
+        assert fused(tile_sum=null, R_enc=0, nparams=5) == NULL, name
+
+
 def _cfg(dtype="bf16", h=256, d=32, device="cpu"):
     return {"seed": 49, "batch_size": 64, "buffer_mult": 128, "lr": 5e-5, "num_tokens": 640, "l1_coeff": 2,
             "beta1": 0.9, "beta2": 0.999, "dict_size": h, "seq_len": 1024, "enc_dtype": dtype, "device": device,

@@ -1503,6 +1503,59 @@ def test_grad_tail_sums_match_separate_launches(gpu, dtype, zero_mask):
     assert (res[0][3][3].item() == 0.0) == bool(zero_mask)
 
 
+def test_fused_wgrad_tail_fallback_matches_separate_launches_and_carries_the_abort_word(gpu):
+    """Where the ping-pong GEMM does not serve the call (fp32 always), cc_wgrad_both_clip_t / cc_wgrad_both_sums_t run
+    cc_wgrad_both_t and then the stand-alone grad tail themselves: the outputs of wgrad_both_t + grad_tail /
+    grad_tail_sums bit for bit, and the tail they launch is handed the step's abort word -- set, the coefficient is
+    CLIP_ABORTED and every per-parameter sum -inf (include/crosscoder_hip.h)."""
+    B, n, d, h = 32, 2, 32, 128
+    K, R1, R2 = n * d, 2, 2
+    g = torch.Generator().manual_seed(11)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(gpu)  # noqa: E731
+    actsT, g_reconT, g_preT, xT = rnd(h, B).relu(), rnd(K, B), rnd(h, B), rnd(K, B)
+    W_dec, inv_norms, colsum = rnd(h, K), rnd(h, n).abs(), actsT.sum(1)
+    gpc, lpc = rnd(R1, h), rnd(R2, K)
+    nw, nr1, nr2 = ops.wgrad_parts(h, K, torch.float32), ops.reduce_parts(h), ops.reduce_parts(K)
+    off = [0, nw, 2 * nw, 2 * nw + nr1, 2 * nw + nr1 + nr2]
+    tile_sum = torch.zeros(ops.wgrad_tile_sums(h, K), device=gpu)
+    flag = torch.ones(1, dtype=torch.int32, device=gpu)
+
+    def run(form, fused, zero_mask=0, abort_ptr=None):
+        sq = torch.rand(off[-1], generator=torch.Generator().manual_seed(12)).to(gpu)
+        gd, ge = torch.empty(h, K, device=gpu), torch.empty(h, K, device=gpu)
+        gbe, gbd = torch.empty(h, device=gpu), torch.empty(K, device=gpu)
+        out = torch.full((8,), float("nan"), device=gpu)
+        ctr = torch.zeros(1, dtype=torch.int32, device=gpu)
+        wgrad = (actsT, g_reconT, W_dec, inv_norms, colsum, 2.0 / B, gd, sq[off[1]:off[2]], g_preT, xT, ge,
+                 sq[off[0]:off[1]], n, d)
+        bias = (gpc, gbe, sq[off[2]:off[3]], lpc, gbd, sq[off[3]:off[4]])
+        if not fused:
+            ops.wgrad_both_t(*wgrad)
+        if form == "clip":
+            if fused:
+                ops.wgrad_both_clip_t(*wgrad, *bias, sq, off, 1.0, False, out, ctr, tile_sum, abort_ptr=abort_ptr)
+            else:
+                ops.grad_tail(*bias, sq, off, 1.0, False, out, ctr)
+        elif fused:
+            ops.wgrad_both_sums_t(*wgrad, *bias, sq, off, out, ctr, tile_sum, zero_mask=zero_mask, abort_ptr=abort_ptr)
+        else:
+            ops.grad_tail_sums(*bias, sq, off, out, ctr, zero_mask=zero_mask)
+        torch.cuda.synchronize()
+        assert int(ctr.item()) == 0
+        return gd, ge, gbe, gbd, sq, out
+
+    for form, zero_mask, n_out in (("clip", 0, 6), ("sums", 0, 4), ("sums", 0b0101, 4)):
+        fused, sep = run(form, True, zero_mask), run(form, False, zero_mask)
+        for a, b in zip(fused[:5], sep[:5]):
+            assert torch.equal(a, b), form
+        assert torch.equal(fused[5][:n_out], sep[5][:n_out]) and bool(torch.isfinite(sep[5][:n_out]).all()), form
+        if form == "sums":
+            assert [v == 0.0 for v in fused[5][:4].tolist()] == [bool(zero_mask >> p & 1) for p in range(4)]
+    assert 0.0 < run("clip", True)[5][0].item() <= 1.0
+    assert run("clip", True, abort_ptr=flag.data_ptr())[5][0].item() == ops.CLIP_ABORTED
+    assert run("sums", True, 0b0101, abort_ptr=flag.data_ptr())[5][:4].tolist() == [float("-inf")] * 4
+
+
 # ----------------------------------------------------------------------------- BASELINE configs 4 / 5 shapes
 @pytest.mark.parametrize("B,n,d,h", [(8192, 2, 3584, 8192),     # config 4 per-GPU shard (2x3584->65536 / 8)
                                      (4096, 4, 2304, 32768)])   # config 5: 4x2304->32768 on one GPU
