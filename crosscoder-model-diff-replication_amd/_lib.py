@@ -16,7 +16,7 @@ DEFAULT_PP_MASK = 7  # the ping-pong layouts both libraries default to (csrc/gem
 _INT_SETTERS = ("cc_debug_set_pp_mask", "cc_debug_set_pp_fast", "cc_debug_set_dec_one_launch",
                 "cc_debug_set_wave_sync", "cc_debug_set_epi_store", "cc_debug_set_q4", "cc_debug_set_adam_ref")
 # what the debug build exports beyond the header and its probes: the setters, and the exhaustive check of the
-# bf16 Adam's fast primitives against their references (csrc/step_kernels.hip: cc_debug_adam_prims)
+# bf16 Adam's fast primitives against their references (csrc/adam.hip: cc_debug_adam_prims)
 # (named for the setters; test_cpu_host.py checks the debug build's exports against this tuple)
 DEBUG_SETTERS = _INT_SETTERS + ("cc_debug_adam_prims", "cc_debug_adam_redone")
 

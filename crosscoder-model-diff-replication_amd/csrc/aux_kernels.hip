@@ -174,8 +174,6 @@ __global__ __launch_bounds__(64) void norms_finalize_kernel(const float* __restr
   if (row < h) norms_finalize_row(part, row, n, bpm, norms, total, inv_norms);
 }
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 }  // namespace cc
 
 using namespace cc;

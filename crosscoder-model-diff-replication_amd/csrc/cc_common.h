@@ -190,9 +190,20 @@ CC_DEV void norms_finalize_row(const float* __restrict__ part, int row, int n, i
   total[row] = tot;
 }
 
+// host side: a pointer the kernels' 16-byte vector accesses can take
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace cc
 
-#define CC_LAUNCH_CHECK()                                \
+// KERNEL_CALL with DT_ = dtype as a constant; any other dtype returns CC_ERR_DTYPE from the calling function
+#define DISPATCH_DT(dtype, KERNEL_CALL)                                   \
+  do {                                                                    \
+    if ((dtype) == CC_BF16) { constexpr int DT_ = CC_BF16; KERNEL_CALL; } \
+    else if ((dtype) == CC_F32) { constexpr int DT_ = CC_F32; KERNEL_CALL; } \
+    else return CC_ERR_DTYPE;                                             \
+  } while (0)
+
+#define CC_LAUNCH_CHECK()                               \
   do {                                                   \
     hipError_t e__ = hipGetLastError();                  \
     if (e__ != hipSuccess) return CC_ERR_HIP_BASE + (int)e__; \

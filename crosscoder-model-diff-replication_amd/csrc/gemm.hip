@@ -853,8 +853,6 @@ static int launch_dt(int dtype, GemmArgs a, hipStream_t st) {
   return CC_ERR_DTYPE;
 }
 
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // Shape / alignment validation shared by all GEMM entries.
 static int check_gemm(const GemmArgs& a, int dtype, bool akc, bool bkc) {
   if (!a.A || !a.B) return CC_ERR_NULL;

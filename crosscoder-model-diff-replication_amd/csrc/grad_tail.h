@@ -3,7 +3,8 @@
 // reductions of partial slabs and the clip_grad_norm_ finaliser (device side); the tail's kernel
 // arguments TailArgs, the one host builder that checks and fills them for every launch form
 // (make_grad_tail_args, as make_loss_tail_args for the loss tail) and the stand-alone launcher's
-// declaration (host side).  Included inside namespace cc.
+// declaration (host side).  The Adam kernels that form the clip coefficient themselves (adam.hip: adam_coef) take
+// clip_param_norm and clip_coef from here.  Included inside namespace cc.
 #pragma once
 
 // ---------------------------------------------------------------------------------------
@@ -158,7 +159,7 @@ CC_DEV void clip_finish(const ClipArgs& a, const double* s, double (*red)[NT / 6
       const int p = threadIdx.x;
       // (the step was aborted -- G2's in-kernel wait timed out, ClipArgs::abort: -inf for every parameter, so the
       // sums' all-reduce carries the abort to every rank and each Adam launch that forms its coefficient from them
-      // applies nothing, adam_coef.  Each of these threads reads the word itself.)
+      // applies nothing, adam.hip's adam_coef.  Each of these threads reads the word itself.)
       const bool ab = a.abort && __hip_atomic_load(a.abort, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) != 0u;
       double t = 0.0;
       for (int w = 0; w < NT / 64; ++w) t += red[p][w];
@@ -217,24 +218,34 @@ struct GradTailIn {
   uint32_t* counter;
   const uint32_t* abort;
 };
+// The squared-sum segments sq / off / nparams and the output of a ClipArgs, checked (NULL, then nparams) and filled;
+// everything else zero.  Every launch that runs clip_body starts from it: cc_clip_finalize, cc_segment_sums and the
+// grad tail.
+static inline int make_clip_args(ClipArgs& a, const float* sq, const int64_t* off, int nparams, float* out) {
+  if (!sq || !off || !out) return CC_ERR_NULL;
+  if (nparams <= 0 || nparams > 8) return CC_ERR_SHAPE;
+  a = ClipArgs{};
+  a.sq = sq;
+  for (int i = 0; i <= nparams; ++i) a.off[i] = off[i];
+  a.nparams = nparams;
+  a.out = out;
+  return CC_OK;
+}
 // The only copy of the tail's argument checks (NULL, then the shapes, then nparams) and of the field fill.
 static inline int make_grad_tail_args(TailArgs& a, const GradTailIn& in) {
+  // (the clip's pointers too: a NULL one is reported before a wrong shape)
   if (!in.gpre_colpart || !in.g_b_enc || !in.sq_b_enc || !in.loss_colpart || !in.g_b_dec || !in.sq_b_dec || !in.sq ||
       !in.off || !in.out || !in.counter)
     return CC_ERR_NULL;
   if (in.R_enc <= 0 || in.R_dec <= 0 || in.h <= 0 || in.K <= 0) return CC_ERR_SHAPE;
-  if (in.nparams <= 0 || in.nparams > 8) return CC_ERR_SHAPE;
   a = TailArgs{};
+  if (const int rc = make_clip_args(a.clip, in.sq, in.off, in.nparams, in.out)) return rc;
   a.red[0] = {in.gpre_colpart, (int)in.R_enc, (int)in.h, in.h, 1.f, nullptr, in.g_b_enc, in.sq_b_enc, nullptr, nullptr};
   a.red[1] = {in.loss_colpart, (int)in.R_dec, (int)in.K, in.K, 1.f, nullptr, in.g_b_dec, in.sq_b_dec, nullptr, nullptr};
   a.red_blocks[0] = (int)((in.h + RED_COLS - 1) / RED_COLS);
   a.red_blocks[1] = (int)((in.K + RED_COLS - 1) / RED_COLS);
-  a.clip.sq = in.sq;
-  for (int i = 0; i <= in.nparams; ++i) a.clip.off[i] = in.off[i];
-  a.clip.nparams = in.nparams;
   a.clip.max_norm = in.max_norm;
   a.clip.emulate_bf16 = in.emulate_bf16;
-  a.clip.out = in.out;
   a.clip.sums_only = in.sums_only;
   a.clip.zero_mask = in.zero_mask;
   a.clip.abort = in.abort;

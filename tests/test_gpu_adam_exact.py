@@ -1,4 +1,4 @@
-"""The bf16 Adam's fast arithmetic (csrc/step_kernels.hip: adam_sqrt2, adam_udiv, adam_quot2, adam_pair) against the
+"""The bf16 Adam's fast arithmetic (csrc/adam.hip: adam_sqrt2, adam_udiv, adam_quot2, adam_pair) against the
 reference arithmetic it replaced (adam_elem: IEEE divisions, correctly rounded sqrtf), bit for bit.  The test
 library evaluates each primitive and its reference over a whole domain on the device (cc_debug_adam_prims) and can
 run every Adam entry on the reference arithmetic (cc_debug_set_adam_ref).  Two NaNs count as equal; everything

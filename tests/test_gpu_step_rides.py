@@ -28,9 +28,18 @@ def _adam_operands(numel, gpu, seed):
     return p, gr, m, v
 
 
-@pytest.mark.parametrize("in_dtype,factor_dtype", [(bf16, bf16), (torch.float32, torch.float32), (bf16, None)])
-@pytest.mark.parametrize("B,d", [(256, 64), (264, 64), (256, 128), (264, 128)])
-@pytest.mark.parametrize("coef", [0.37, -1.0])
+PREP_JOBS = [pytest.param(coef, B, d, pair[0], pair[1],
+                          id=f"{coef}-{B}-{d}-in_dtype{k}-" + ("None" if pair[1] is None else f"factor_dtype{k}"))
+             for k, pair in enumerate(((bf16, bf16), (torch.float32, torch.float32), (bf16, None)))
+             for B, d in ((256, 64), (264, 64), (256, 128), (264, 128))
+             for coef in (0.37, -1.0)]
+# the other two (input, factor) dtype pairs, so that every pair runs with a factor that is read: one full 64-row
+# block + 8 rows, K = 144 past one 128-column narrow block
+PREP_JOBS += [pytest.param(0.37, 72, 72, torch.float32, bf16, id="0.37-72-72-fp32-bf16"),
+              pytest.param(0.37, 72, 72, bf16, torch.float32, id="0.37-72-72-bf16-fp32")]
+
+
+@pytest.mark.parametrize("coef,B,d,in_dtype,factor_dtype", PREP_JOBS)
 def test_adam_with_prep_job_matches_the_two_launches(gpu, B, d, in_dtype, factor_dtype, coef):
     """cc_adam_step_prep against cc_adam_step then cc_prep_input_t: p, m, v, x, x^T and the column-sum partials.
     B 264: a last row block of 8 rows; h 520: a last Adam workgroup that is not full; coef -1 (CC_CLIP_ABORTED): no

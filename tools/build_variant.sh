@@ -8,7 +8,7 @@ OUT=$ROOT/crosscoder-model-diff-replication_amd/exp
 B=/tmp/variant_$1
 mkdir -p "$OUT" "$B"
 F="-O3 -std=c++17 --offload-arch=gfx950 -fPIC -fvisibility=hidden -Wall -Wno-unused-function -munsafe-fp-atomics $2"
-for s in gemm step_kernels aux_kernels; do
+for s in gemm step_kernels adam aux_kernels; do
   /opt/rocm/bin/hipcc $F -c "$SRC/$s.hip" -o "$B/$s.o" &
 done
 wait
