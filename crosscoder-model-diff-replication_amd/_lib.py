@@ -153,6 +153,9 @@ SIGNATURES = {
     "cc_jumprelu_mask": (_i, [_p, _i64, _i64, _i64, _i, _p, _f, _p, _p, _p, _p, _p]),
     "cc_jumprelu_bwd": (_i, [_p, _p, _i64, _i64, _i64, _i, _p, _f, _f, _p, _p, _p]),
     "cc_decode_pairs": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i64, _p, _p]),
+    "cc_row_norms": (_i, [_p, _i64, _i64, _i64, _i, _p, _p]),
+    "cc_resample_pick": (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
+    "cc_resample_write": (_i, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i, _f, _f, _p, _p, _p, _p, _i, _p, _p]),
 }
 
 _lib = None

@@ -400,6 +400,17 @@ def flush_norms(ws):
             ops.dec_norms_finalize(ws.norm_part, ws.h, ws.n, ws.d, ws.norms, ws.tn, ws.inv_norms)
 
 
+def invalidate_decoder_derived(ws):
+    """After a kernel other than the step's Adam wrote W_dec (resample.py): drop what the workspace carries from the
+    last Adam launch to the next forward, which then re-derives it from W_dec (decoder_norms).  The token alone does
+    not do: it is keyed on torch's version counter, which a kernel write does not bump, and norm partials pending
+    their finaliser (norms_fin_pending, set by the first reader's wait for the side-stream Adam) would be finalised
+    over the re-derived norms by the next G2 launch.  Call it after Arena.wait_pending()."""
+    if ws is not None:
+        ws.norms_token = None
+        ws.norms_fin_pending = False
+
+
 def decoder_norms(ws, P):
     """||W_dec[h, m]||, their sum over m and inverses (crosscoder.py:123-125), unless still fresh."""
     if getattr(ws, "norms_token", None) == _norms_token(P):

@@ -1018,3 +1018,74 @@ def jumprelu_bwd(g_pre, gate, h, theta, eps, l0_scale, gpre_colsum_part=None, th
                            (("gpre_colsum_part", gpre_colsum_part), ("thr_part", thr_part)))
     check(lib().cc_jumprelu_bwd(_ptr(g_pre), _ptr(gate), ld, B, h, dtype_code(g_pre.dtype), _ptr(theta), float(eps),
                                 float(l0_scale), _ptr(gpre_colsum_part), _ptr(thr_part), _stream(g_pre)))
+
+
+# ---------------------------------------------------------------- dead-latent resampling (resample.py)
+def row_norms(W, out=None):
+    """out fp32 [rows] <- the 2-norm of every row of W [rows, K] (bf16 / fp32, K % 8 == 0; a column slice of a wider
+    matrix keeps its row pitch), one pass in a fixed order (cc_row_norms): no fp32 copy of W is made."""
+    if W.dim() != 2 or W.shape[0] < 1:
+        raise ValueError(f"W must be [rows >= 1, K], got {tuple(W.shape)}")
+    rows, K = W.shape
+    if out is None:
+        out = torch.empty(rows, dtype=torch.float32, device=W.device)
+    _dense(out, torch.float32, (rows,), W.device, "out")
+    pw, ld = _pitched(W, K, "W")
+    check(lib().cc_row_norms(pw, ld, rows, K, dtype_code(W.dtype), _ptr(out), _stream(W)))
+    return out
+
+
+def resample_pick(loss, u, cdf=None, rows_out=None):
+    """rows_out int64 [J] <- for every uniform u[j] (fp64 in [0, 1)) a row of loss (fp32 [R]) drawn with probability
+    proportional to loss^2 (fp64; a negative or non-finite loss never), with replacement: the smallest r whose
+    inclusive prefix sum cdf[r] exceeds u[j] * cdf[R - 1] (cc_resample_pick).  cdf: fp64 [R] scratch that receives
+    the prefix sums.  No row has weight: every entry is -1.  -> (rows_out, cdf)"""
+    dev = loss.device
+    if loss.dim() != 1 or loss.shape[0] < 1 or u.dim() != 1 or u.shape[0] < 1:
+        raise ValueError(f"loss [R >= 1] and u [J >= 1] expected, got {tuple(loss.shape)} and {tuple(u.shape)}")
+    R, J = loss.shape[0], u.shape[0]
+    _dense(loss, torch.float32, (R,), dev, "loss")
+    _dense(u, torch.float64, (J,), dev, "u")
+    if cdf is None:
+        cdf = torch.empty(R, dtype=torch.float64, device=dev)
+    if rows_out is None:
+        rows_out = torch.empty(J, dtype=torch.int64, device=dev)
+    _dense(cdf, torch.float64, (R,), dev, "cdf")
+    _dense(rows_out, torch.int64, (J,), dev, "rows_out")
+    check(lib().cc_resample_pick(_ptr(loss), R, _ptr(u), J, _ptr(cdf), _ptr(rows_out), _stream(loss)))
+    return rows_out, cdf
+
+
+def resample_write(X, rows, latents, h, enc_norm, dec_norm, params, master=None, exp_avg=None, exp_avg_sq=None,
+                   done=None):
+    """Re-seed latent latents[j] from the pool row X[rows[j]] for every j (cc_resample_write): its W_dec row becomes
+    x * dec_norm / ||x||, its W_enc row x * enc_norm / ||x||, its b_enc 0, in `params` (the flat arena
+    [W_enc [h][K] | b_enc [h] | W_dec [h][K] | b_dec [K]] of X's dtype) and unrounded in `master` (fp32, the same
+    layout); the latent's rows and b_enc entries of exp_avg / exp_avg_sq (one dtype, together) become 0.  X [R, K]
+    (rows contiguous); rows, latents int64 [J], latents distinct and in [0, h) (the caller's check); a row index
+    outside [0, R) or a source row of zeros leaves its latent untouched.  done (int32 [J], allocated if not given)
+    says which were written.  -> done"""
+    R, ldx = _rows_ld(X, "X")
+    K, dev = X.shape[1], X.device
+    numel = 2 * h * K + h + K
+    J = rows.shape[0] if rows.dim() == 1 else -1
+    if J < 1:
+        raise ValueError(f"rows must be int64 [J >= 1], got {tuple(rows.shape)}")
+    _dense(rows, torch.int64, (J,), dev, "rows")
+    _dense(latents, torch.int64, (J,), dev, "latents")
+    _dense(params, X.dtype, (numel,), dev, "params")
+    _dense(master, torch.float32, (numel,), dev, "master")
+    if (exp_avg is None) != (exp_avg_sq is None):
+        raise ValueError("exp_avg and exp_avg_sq go together")
+    sdt = CC_F32
+    if exp_avg is not None:
+        sdt = dtype_code(exp_avg.dtype)
+        _dense(exp_avg, exp_avg.dtype, (numel,), dev, "exp_avg")
+        _dense(exp_avg_sq, exp_avg.dtype, (numel,), dev, "exp_avg_sq")
+    if done is None:
+        done = torch.empty(J, dtype=torch.int32, device=dev)
+    _dense(done, torch.int32, (J,), dev, "done")
+    check(lib().cc_resample_write(_ptr(X), ldx, R, _ptr(rows), _ptr(latents), J, h, K, dtype_code(X.dtype),
+                                  float(enc_norm), float(dec_norm), _ptr(params), _ptr(master), _ptr(exp_avg),
+                                  _ptr(exp_avg_sq), sdt, _ptr(done), _stream(X)))
+    return done

@@ -299,6 +299,9 @@ class ShardedTrainer:
             raise ValueError("ShardedTrainer does not serve master_weights: its Adam launches form the clip coefficient "
                              "from the all-reduced sums (cc_adam_step_clip), which the master-weight update does not "
                              "take; train with Trainer")
+        if cfg.get("resample_every", 0) or crosscoder_cfg.get("resample_every", 0):
+            raise ValueError("ShardedTrainer does not serve resample_every: a dead latent's source row is drawn from "
+                             "the whole dictionary's reconstruction loss, which no rank holds; resample with Trainer")
         self.group = group
         self.rank = dist.get_rank(group)
         self.world = dist.get_world_size(group)

@@ -9,6 +9,8 @@ reference's) lives in arenas mirroring the parameter arena, exposed through
 `optimizer.state[param]` for inspection.  cfg["master_weights"] = True (bf16 crosscoders) keeps fp32 master weights and
 fp32 moments instead, the bf16 parameters being the masters rounded after every update (DESIGN.md section 3.16);
 `Trainer.state_dict()` / `load_state_dict()` carry the optimizer's state across a restart in either mode.
+cfg["resample_every"] = N re-seeds the dead latents after every N-th step (dead-latent resampling, DESIGN.md section
+3.18; `Trainer.resample_dead_latents` is the same between steps of the caller's choosing).
 """
 import torch
 import tqdm
@@ -16,6 +18,32 @@ import tqdm
 from . import _hip, engine
 from .buffer import Buffer
 from .crosscoder import CrossCoder, master_weights_of
+from .resample import LatentResampler
+
+RESAMPLE_ROWS = 819200  # cfg["resample_rows"]'s default: the pool of "Towards Monosemanticity"'s neuron resampling
+
+
+def resample_options(cfg):
+    """(resample_every, resample_rows, resample_enc_scale) of a cfg (framework extension), or None when periodic
+    dead-latent resampling is off.  cfg["resample_every"]: an int >= 0 of steps, absent or 0: off.  On, Trainer.step
+    re-seeds the dead latents after every resample_every-th step before the LR decay starts (0.8 of the run), from a
+    pool of cfg["resample_rows"] // batch_size batches (an int >= batch_size, default 819 200) that it draws with
+    buffer.next() -- those batches are consumed: the steps that follow train on the ones after them -- and with
+    cfg["resample_enc_scale"] (a float > 0, default 0.2) as LatentResampler's enc_scale."""
+    every = cfg.get("resample_every", 0)
+    if isinstance(every, bool) or not isinstance(every, int) or every < 0:
+        raise ValueError(f"cfg['resample_every'] must be an int >= 0 (steps), got {every!r}")
+    if every == 0:
+        return None
+    if cfg.get("activation", "relu") == "jumprelu":
+        raise ValueError("cfg['resample_every'] is not served with activation 'jumprelu' (LatentResampler)")
+    rows = cfg.get("resample_rows", max(RESAMPLE_ROWS, cfg["batch_size"]))
+    if isinstance(rows, bool) or not isinstance(rows, int) or rows < cfg["batch_size"]:
+        raise ValueError(f"cfg['resample_rows'] must be an int >= batch_size ({cfg['batch_size']}), got {rows!r}")
+    scale = cfg.get("resample_enc_scale", 0.2)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not scale > 0 or scale == float("inf"):
+        raise ValueError(f"cfg['resample_enc_scale'] must be a finite float > 0, got {scale!r}")
+    return every, rows, float(scale)
 
 
 def reference_loss(l2, l1, l1c, dtype):
@@ -222,6 +250,9 @@ class Trainer:
         self.auxk = self.crosscoder.auxk
         self._tsf = None
         self._dead_count = 0
+        # periodic dead-latent resampling (resample_options); the pool is allocated with the first resample
+        self.resample = resample_options(cfg)
+        self._resampler = None
 
     def lr_lambda(self, step):
         if step < 0.8 * self.total_steps:
@@ -416,7 +447,50 @@ class Trainer:
             loss_dict["loss"] = jumprelu_loss(loss_dict["loss"], l0, l0c)
             loss_dict["l0_coeff"] = l0c
         self.step_counter += 1
+        if (self.resample is not None and self.step_counter % self.resample[0] == 0
+                and self.step_counter < 0.8 * self.total_steps):
+            loss_dict["resampled"] = self._resample_from_buffer()
         return loss_dict
+
+    def _resample_from_buffer(self):
+        """cfg["resample_every"]'s resample: a pool of resample_rows // batch_size batches drawn with buffer.next()
+        (consumed: the next step trains on the batch after them), the latents that fired on none of them re-seeded
+        with uniforms from a generator seeded with cfg["seed"] and the step.  -> the number re-seeded."""
+        _, rows, enc_scale = self.resample
+        B = self.cfg["batch_size"]
+        rs = self._resampler
+        if rs is None or rs.cc.arena().data.device != rs._x.device:
+            rs = self._resampler = LatentResampler(self.crosscoder, rows // B * B, enc_scale=enc_scale,
+                                                   seed=self.cfg["seed"])
+        rs.reset()
+        self.synchronize()
+        for _ in range(rows // B):
+            rs.add(self.buffer.next())
+        J = int(rs.dead().sum())
+        gen = torch.Generator(device="cpu").manual_seed((self.cfg["seed"] * 1000003 + self.step_counter) % (1 << 63))
+        u = torch.rand(J, dtype=torch.float64, generator=gen)
+        return self.resample_dead_latents(rs, u=u)["resampled"]
+
+    def resample_dead_latents(self, resampler, dead=None, u=None):
+        """Re-seed dead latents between two steps (LatentResampler.apply with this trainer's optimizer): orders
+        torch's current stream after the last step's launches on both of its streams, applies `resampler` (built on
+        this trainer's crosscoder and filled by the caller; dead, u: apply's), drops what the last step's workspace
+        carries of the old decoder, and -- AuxK trainers -- zeroes tokens_since_fired of the re-seeded latents and
+        refreshes the dead count.  Returns apply's dict."""
+        if resampler.cc is not self.crosscoder:
+            raise ValueError("resampler must be built on this trainer's crosscoder")
+        self.synchronize()
+        dev = self.crosscoder.arena().data.device
+        if self._side is not None:
+            torch.cuda.current_stream(dev).wait_stream(self._side)
+        out = resampler.apply(self.optimizer, dead=dead, u=u)
+        if out["resampled"]:
+            engine.invalidate_decoder_derived(self._last_ws)
+            if self.auxk is not None:
+                tsf = self._since_fired()
+                tsf[out["latents"][out["written"]]] = 0
+                self._dead_count = int((self.tokens_since_fired >= self.auxk[2]).sum())
+        return out
 
     def log(self, loss_dict):
         if self.logger is not None:

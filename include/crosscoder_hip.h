@@ -735,6 +735,54 @@ int cc_decode_pairs(const void* val, const int32_t* idx, int64_t B, int k, const
                     const void* b_dec, int64_t n, int64_t d, int dtype, void* recon, int64_t ldr, const void* x,
                     int64_t ldx, float* sq_err, void* stream);
 
+/* ---- Dead-latent resampling (LatentResampler; Anthropic's neuron resampling for L1 dictionaries): a dead latent is
+ * re-seeded from an input the dictionary reconstructs badly.  No float atomics, no spin waits, fixed summation orders:
+ * two calls on the same input give the same bits in every output.
+ *
+ * cc_row_norms: out[r] (fp32) = sqrt(sum_c float(W[r][c])^2) for a [rows][K] matrix of row pitch ld (elements), one
+ * pass, no copy of W.  A lane folds its columns' squares into one fp32 fma chain (8 consecutive columns of every
+ * 512-column chunk, chunk after chunk), the wave's 64 sums meet in an xor butterfly: at most 8 ceil(K / 512) + 6
+ * roundings on any path.  Serves W_enc and W_dec alike (both [h][K]).
+ * Errors in this order: CC_ERR_SHAPE (rows < 1, K < 8, K % 8 != 0, ld < K), CC_ERR_NULL, CC_ERR_DTYPE,
+ * CC_ERR_TOO_LARGE (rows or K > 2^31 - 1), CC_ERR_ALIGN (W and its pitch 16 bytes, out 4).
+ *
+ * cc_resample_pick: J draws, with replacement, of a row of loss [R] (fp32) with probability proportional to
+ * w_r = (double)loss_r^2; a loss that is negative (sign set) or not finite has weight 0.
+ *   cdf [R] (fp64, caller scratch) receives the inclusive prefix sum of w, formed so that it is non-decreasing and an
+ *   element of weight 0 has its predecessor's bits (cdf[0] = +0 for w_0 = 0): a lane adds 16 consecutive weights one
+ *   after the other, one thread the 256 lane totals of a 4096-row chunk one after the other, one thread of a
+ *   one-workgroup launch the chunk totals one after the other; an element is (chunk offset) + ((lane offset) + (the
+ *   lane's running sum)).  Its relative error is below (16 + 256 + R / 4096 + 2) 2^-53.
+ *   rows_out[j] (int64) = the smallest r with cdf[r] > t_j, t_j = u_j * cdf[R-1] (u fp64 [J] in [0, 1); a NaN or
+ *   negative u_j counts as 0, and a t_j that is not below cdf[R-1] as the largest double below it), by binary search:
+ *   never a row of weight 0.  cdf[R-1] == 0 (no row has weight): every rows_out[j] = -1.
+ * Up to four launches on `stream` (chunk scans, chunk offsets, their addition, the searches).
+ * Errors in this order: CC_ERR_SHAPE (R < 1, J < 1), CC_ERR_NULL, CC_ERR_TOO_LARGE (R or J > 2^31 - 1), CC_ERR_ALIGN
+ * (loss 4 bytes; u, cdf, rows_out 8).
+ *
+ * cc_resample_write: one workgroup per j < J re-seeds latent l = latents[j] from the pool row x = X[rows[j]]
+ * (X [R][ldx], dtype, its K columns).  The arenas -- params (dtype), master (fp32, optional), exp_avg and exp_avg_sq
+ * (state_dtype, optional, together) -- share the layout [ W_enc [h][K] | b_enc [h] | W_dec [h][K] | b_dec [K] ].
+ *   s = sum_c float(x_c)^2 in fp32 (a lane's fma chain over its 8 columns of every 2048-column chunk, the xor
+ *   butterfly, the four waves in order).  If s is 0 or not finite, or rows[j] is outside [0, R) (the -1 of an empty
+ *   pick) or l outside [0, h), nothing is written for j.  Otherwise, with es = enc_norm / sqrtf(s) and
+ *   ds = dec_norm / sqrtf(s) (fp32):
+ *     W_enc[l][c] = dtype(float(x_c) * es),  W_dec[l][c] = dtype(float(x_c) * ds),  b_enc[l] = 0;
+ *     master: the same fp32 products unrounded (so a bf16 parameter is its master rounded to nearest-even) and 0;
+ *     exp_avg, exp_avg_sq: row l of both halves and the b_enc entry become +0.
+ *   b_dec and every other row are not touched.  done (optional, int32 [J]): 1 where j was written, else 0.
+ * latents must be distinct (the caller's check: two workgroups would write one row); rows may repeat.
+ * Errors in this order: CC_ERR_SHAPE (R or J < 1, h or K < 8 or not a multiple of 8, ldx < K), CC_ERR_NULL (X, rows,
+ * latents or params missing, one moment arena without the other), CC_ERR_DTYPE (dtype; state_dtype where the moments
+ * are given), CC_ERR_TOO_LARGE (R, J, h or K > 2^31 - 1), CC_ERR_ALIGN (16 bytes: X and its pitch and every arena;
+ * 8: rows, latents; 4: done). */
+int cc_row_norms(const void* W, int64_t ld, int64_t rows, int64_t K, int dtype, float* out, void* stream);
+int cc_resample_pick(const float* loss, int64_t R, const double* u, int64_t J, double* cdf, int64_t* rows_out,
+                     void* stream);
+int cc_resample_write(const void* X, int64_t ldx, int64_t R, const int64_t* rows, const int64_t* latents, int64_t J,
+                      int64_t h, int64_t K, int dtype, float enc_norm, float dec_norm, void* params, float* master,
+                      void* exp_avg, void* exp_avg_sq, int state_dtype, int32_t* done, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
