@@ -13,6 +13,7 @@ from .latent_stats import LatentStats  # noqa: F401
 from .latent_scaling import LatentScaling  # noqa: F401
 from .decoder_match import match_decoders  # noqa: F401
 from .ablation import LatentAblation  # noqa: F401
+from .attribution import LatentAttribution  # noqa: F401
 from .resample import LatentResampler  # noqa: F401
 
 __version__ = "0.1.0"

@@ -156,6 +156,10 @@ SIGNATURES = {
     "cc_row_norms": (_i, [_p, _i64, _i64, _i64, _i, _p, _p]),
     "cc_resample_pick": (_i, [_p, _i64, _p, _i64, _p, _p, _p]),
     "cc_resample_write": (_i, [_p, _i64, _i64, _p, _p, _i64, _i64, _i64, _i, _f, _f, _p, _p, _p, _p, _i, _p, _p]),
+    "cc_pairs_grad_values": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _p, _i64, _i64, _i64, _i, _p, _p, _p]),
+    "cc_pairs_grad_decoder_ws_floats": (_i64, [_i64, _i64]),
+    "cc_pairs_grad_decoder": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _i64, _i, _p, _i64, _p, _p]),
+    "cc_pairs_latent_sums": (_i, [_p, _i64, _i, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -446,10 +446,16 @@ class CrossCoder(nn.Module):
             indices = indices.clamp(min=-1, max=self.d_hidden).to(torch.int32)
         return values.to(self.dtype).contiguous(), indices.contiguous()
 
-    def decode_pairs(self, values, indices):
+    def decode_pairs(self, values, indices, differentiable=False):
         """(values, indices) [rows, k] as encode_pairs / encode_topk give them -> [rows, n_models, d_model] incl. b_dec:
         the sparse counterpart of decode (cc_decode_pairs: k decoder rows gathered per token, an fp32 sum in slot
-        order rounded once).  A slot whose index is outside [0, dict_size) -- the -1 padding -- adds nothing."""
+        order rounded once).  A slot whose index is outside [0, dict_size) -- the -1 padding -- adds nothing.
+        differentiable=True: the same forward as one autograd node whose backward gives the gradients with respect to
+        values (0 at such slots), W_dec and b_dec from gather kernels (cc_pairs_grad_values, cc_pairs_grad_decoder);
+        no [rows, dict_size] matrix is formed in either direction."""
+        if differentiable:
+            vals, idx = self._pairs(values, indices)
+            return _DecodePairsFn.apply(self, vals, idx, self.W_dec, self.b_dec)
         a = self.arena()
         a.wait_pending()
         vals, idx = self._pairs(values, indices)
@@ -476,6 +482,23 @@ class CrossCoder(nn.Module):
             ops.decode_pairs(vals, idx, a.W_dec_hk, a.b_dec_flat, self.n_models, self._dp, h=self.d_hidden,
                              x=self._flat_x(x), sq_err=sq)
         return sq
+
+    def pairs_attribution(self, values, indices, g):
+        """fp32 [rows, k, n_models]: per pair and model, value * <g[row, model], W_dec[latent, model]> -- the first-order
+        effect of the pair on a metric whose gradient with respect to the reconstruction is g [rows, n_models, d_model]
+        (cc_pairs_grad_values: k decoder rows gathered per token, the row of g read once).  +0 at a slot whose index
+        is outside [0, dict_size)."""
+        a = self.arena()
+        a.wait_pending()
+        vals, idx = self._pairs(values, indices)
+        B, k = vals.shape
+        self._check_x(g)
+        if g.shape[0] != B:
+            raise ValueError(f"g has {g.shape[0]} rows, the pairs {B}")
+        if not B:
+            return torch.empty(0, k, self.n_models, dtype=torch.float32, device=vals.device)
+        return ops.pairs_grad_values(idx, a.W_dec_hk, self._flat_x(g.detach()), self.n_models, self._dp, val=vals.detach(),
+                                     h=self.d_hidden)[0]
 
     def decode(self, acts):
         """acts [batch, d_hidden] -> [batch, n_models, d_model] incl. b_dec (crosscoder.py:82-89)."""
@@ -629,3 +652,44 @@ class _LossFn(torch.autograd.Function):
         ws.busy = None
         v = G.views()
         return None, None, None, v["W_enc"], v["W_dec"], v["b_enc"], v["b_dec"]
+
+
+class _DecodePairsFn(torch.autograd.Function):
+    """decode_pairs(..., differentiable=True) as one autograd node over the sparse decode and its gather backward."""
+
+    @staticmethod
+    def forward(ctx, cc, vals, idx, W_dec, b_dec):
+        a = cc.arena()
+        a.wait_pending()
+        B = vals.shape[0]
+        out = torch.empty(B, cc.n_models * cc._dp, dtype=cc.dtype, device=vals.device)
+        if B:
+            ops.decode_pairs(vals, idx, a.W_dec_hk, a.b_dec_flat, cc.n_models, cc._dp, h=cc.d_hidden, recon=out)
+        ctx.cc = cc
+        ctx.save_for_backward(vals, idx)
+        out = out.view(B, cc.n_models, cc._dp)
+        return out[:, :, :cc.cfg["d_in"]].contiguous() if cc._dp != cc.cfg["d_in"] else out
+
+    @staticmethod
+    def backward(ctx, g):
+        cc = ctx.cc
+        vals, idx = ctx.saved_tensors
+        a = cc.arena()
+        a.wait_pending()
+        n, dp, h, d_in = cc.n_models, cc._dp, cc.d_hidden, cc.cfg["d_in"]
+        B = vals.shape[0]
+        gf = cc.pad_input(g).to(cc.dtype).contiguous().view(B, n * dp)
+        g_vals = g_W = g_b = None
+        if ctx.needs_input_grad[1]:
+            g_vals = torch.zeros_like(vals)
+            if B:  # (total: the models' sums in model order, rounded once to the values' dtype)
+                g_vals = ops.pairs_grad_values(idx, a.W_dec_hk, gf, n, dp, h=h, want_dot=False, want_total=True)[1].to(vals.dtype)
+        if ctx.needs_input_grad[3]:
+            dW = torch.zeros(h, n * dp, dtype=cc.dtype, device=vals.device)
+            if B:
+                perm, seg = ops.pairs_by_latent(idx, h)
+                ops.pairs_grad_decoder(perm, seg, vals, gf, n * dp, out=dW)
+            g_W = dW.view(h, n, dp)[:, :, :d_in]
+        if ctx.needs_input_grad[4]:
+            g_b = gf.sum(0, dtype=torch.float32).to(cc.dtype).view(n, dp)[:, :d_in]
+        return None, g_vals, None, g_W, g_b

@@ -832,6 +832,155 @@ def decode_pairs(val, idx, W_dec, b_dec, n, d, h=None, recon=None, x=None, sq_er
     return recon, sq_err
 
 
+# ---------------------------------------------------------------- the sparse decode's backward (pair gradients)
+PAIRS_GRAD_SPLIT = 128  # CC_PAIRS_GRAD_SPLIT (include/crosscoder_hip.h)
+
+
+def _pairs_idx(idx, val, name="val"):
+    """(B, k) of idx [B, k] int32, contiguous; an optional val of the same shape, bf16 / fp32, contiguous, beside it"""
+    if idx.dim() != 2 or idx.shape[0] < 1 or idx.shape[1] < 1 or (val is not None and val.shape != idx.shape):
+        raise ValueError(f"idx (and {name}) must be [rows >= 1, k >= 1], got {tuple(idx.shape)}"
+                         + ("" if val is None else f" and {tuple(val.shape)}"))
+    if idx.dtype != torch.int32:
+        raise ValueError(f"idx must be int32, got {idx.dtype}")
+    if val is not None and val.dtype not in _DT:
+        raise ValueError(f"{name} must be bf16 or fp32, got {val.dtype}")
+    if not idx.is_contiguous() or (val is not None and not val.is_contiguous()):
+        raise ValueError(f"idx and {name} must be contiguous")
+    if val is not None and val.device != idx.device:
+        raise ValueError(f"{name} must be on {idx.device}")
+    return idx.shape
+
+
+def _grouped(perm, seg, dev):
+    """(P, h) of the pairs grouped by latent: perm [P] int32, seg [h + 1] int64, contiguous on dev"""
+    if perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous() or perm.device != dev:
+        raise ValueError(f"perm must be a contiguous int32 vector on {dev}")
+    if seg.dtype != torch.int64 or seg.dim() != 1 or seg.shape[0] < 2 or not seg.is_contiguous() or seg.device != dev:
+        raise ValueError(f"seg must be a contiguous int64 vector of dict_size + 1 >= 2 elements on {dev}")
+    return perm.shape[0], seg.shape[0] - 1
+
+
+def pairs_by_latent(idx, h):
+    """The pairs idx [B, k] (int32 or int64) grouped by latent -> (perm int32 [B k], seg int64 [h + 1]): the first seg[h]
+    entries of perm are the flat slot numbers r * k + s of the valid pairs (0 <= idx < h) sorted by (latent, r, s), and
+    latent j's are perm[seg[j] : seg[j + 1]]; the remaining entries (the invalid slots, in slot order) belong to no
+    segment.  torch on idx's device, no host synchronisation: a sort of the unique int64 keys latent * (B k) + slot
+    (an invalid slot counts as latent h), a count per latent and a cumsum.  Deterministic: the keys are distinct, so
+    every sort gives one order, and the counts are integers."""
+    if idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f"idx must be an int32 or int64 [rows, k] tensor, got {idx.dtype} {tuple(idx.shape)}")
+    if isinstance(h, bool) or not isinstance(h, int) or h < 1:
+        raise ValueError(f"h must be an int >= 1, got {h!r}")
+    Bk = idx.numel()
+    if Bk > 2 ** 31 - 1:
+        raise ValueError(f"rows * k must stay below 2^31, got {Bk}")
+    lat = idx.reshape(-1).to(torch.int64)
+    lat = torch.where((lat >= 0) & (lat < h), lat, torch.full_like(lat, h))
+    keys = lat * Bk + torch.arange(Bk, dtype=torch.int64, device=idx.device)
+    perm = (torch.sort(keys).values % max(Bk, 1)).to(torch.int32)
+    count = torch.zeros(h + 1, dtype=torch.int64, device=idx.device).scatter_add_(0, lat, torch.ones_like(lat))
+    seg = torch.zeros(h + 1, dtype=torch.int64, device=idx.device)
+    torch.cumsum(count[:h], 0, out=seg[1:])
+    return perm, seg
+
+
+def pairs_grad_values(idx, W_dec, g, n, d, val=None, h=None, dot=None, total=None, want_dot=True, want_total=False):
+    """The sampled dot products of g [B, >= n * d] with the decoder rows the pairs name (cc_pairs_grad_values): dot fp32
+    [B, k, n], per slot and model  sum_c g[r, c] * W_dec[idx[r, s], c];  with val [B, k] (g's dtype) multiplied once in
+    fp32 by val[r, s]: the pair's attribution.  total fp32 [B, k]: dot summed over the models in model order.  An
+    output is computed when it is given or wanted (want_dot, want_total: it is then allocated), at least one of them.
+    A slot whose index is outside [0, h) gives +0 (h defaults to W_dec's rows).  idx [B, k] int32, contiguous; W_dec
+    [>= h, >= n * d] and g may be column slices of wider matrices.  -> (dot or None, total or None)."""
+    B, k = _pairs_idx(idx, val)
+    for name, v in (("n", n), ("d", d)):
+        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
+    if d % 8:
+        raise ValueError(f"d must be a multiple of 8, got {d}")
+    K, dt, dev = n * d, g.dtype, idx.device
+    if dt not in _DT:
+        raise ValueError(f"g must be bf16 or fp32, got {dt}")
+    if g.dim() != 2 or g.shape[0] != B or g.shape[1] < K or g.device != dev:
+        raise ValueError(f"g must be [{B}, >= {K}] on {dev}, got {tuple(g.shape)}")
+    if W_dec.dim() != 2 or W_dec.shape[1] < K or W_dec.dtype != dt or W_dec.device != dev:
+        raise ValueError(f"W_dec must be [h, >= {K}] of {dt} on {dev}, got {W_dec.dtype} {tuple(W_dec.shape)}")
+    if val is not None and val.dtype != dt:
+        raise ValueError(f"val must have g's dtype {dt}, got {val.dtype}")
+    h = W_dec.shape[0] if h is None else h
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
+        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
+    _dense(dot, torch.float32, (B, k, n), dev, "dot")
+    _dense(total, torch.float32, (B, k), dev, "total")
+    if dot is None and total is None and not want_dot and not want_total:
+        raise ValueError("at least one of dot and total is needed")
+    (pw, ldw), (pg, ldg) = _pitched(W_dec, K, "W_dec"), _pitched(g, K, "g")
+    stream = _stream(idx)
+    if total is None and want_total:
+        total = torch.empty(B, k, dtype=torch.float32, device=dev)
+    if dot is None and want_dot:
+        dot = torch.empty(B, k, n, dtype=torch.float32, device=dev)
+    check(lib().cc_pairs_grad_values(_ptr(idx), _ptr(val), B, k, pw, ldw, h, pg, ldg, n, d, dtype_code(dt), _ptr(dot),
+                                     _ptr(total), stream))
+    return dot, total
+
+
+def pairs_grad_decoder_ws_floats(P, K):
+    return int(lib().cc_pairs_grad_decoder_ws_floats(P, K))
+
+
+def pairs_grad_decoder(perm, seg, val, g, K, out=None, ws=None):
+    """dW [h, K] (val's dtype) <- pairs^T . g from the pairs grouped by latent (pairs_by_latent; cc_pairs_grad_decoder):
+    row j = sum over latent j's pairs, in perm's order, of val[r, s] * g[r, :K] -- one fp32 fma chain per element (a
+    list longer than PAIRS_GRAD_SPLIT in pieces of that length, added in order), rounded once; a latent without pairs
+    gets a row of +0.  val [B, k] contiguous, g [B, >= K] and out [h, >= K] of its dtype (column slices keep their
+    pitch); ws: fp32, at least pairs_grad_decoder_ws_floats(len(perm), K) elements (allocated when None)."""
+    if val.dim() != 2 or val.shape[0] < 1 or val.shape[1] < 1 or val.dtype not in _DT or not val.is_contiguous():
+        raise ValueError(f"val must be a contiguous bf16 or fp32 [rows >= 1, k >= 1] tensor, got {val.dtype} "
+                         f"{tuple(val.shape)}")
+    B, k = val.shape
+    dt, dev = val.dtype, val.device
+    P, h = _grouped(perm, seg, dev)
+    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
+        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
+    if g.dim() != 2 or g.shape[0] != B or g.shape[1] < K or g.dtype != dt or g.device != dev:
+        raise ValueError(f"g must be [{B}, >= {K}] of {dt} on {dev}, got {g.dtype} {tuple(g.shape)}")
+    if out is not None and (out.dim() != 2 or out.shape[0] != h or out.shape[1] < K or out.dtype != dt
+                            or out.device != dev):
+        raise ValueError(f"out must be [{h}, >= {K}] of {dt} on {dev}, got {out.dtype} {tuple(out.shape)}")
+    need = (P // PAIRS_GRAD_SPLIT) * K
+    if ws is not None and (ws.dtype != torch.float32 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"ws must be a contiguous fp32 tensor of at least {need} elements on {dev}")
+    pg, ldg = _pitched(g, K, "g")
+    stream = _stream(val)
+    if out is None:
+        out = torch.empty(h, K, dtype=dt, device=dev)
+    if ws is None and need:
+        ws = torch.empty(pairs_grad_decoder_ws_floats(P, K), dtype=torch.float32, device=dev)
+    po, ldo = _pitched(out, K, "out")
+    check(lib().cc_pairs_grad_decoder(_ptr(perm), P, _ptr(seg), h, _ptr(val), B, k, pg, ldg, K, dtype_code(dt), po, ldo,
+                                      _ptr(ws), stream))
+    return out
+
+
+def pairs_latent_sums(a, perm, seg, sum, abs_sum, count):
+    """The per-pair values a fp32 [B, k, n] folded into the per-latent state sum / abs_sum fp64 [h, n] and count int64
+    [h], in place (cc_pairs_latent_sums): for latent j and its pairs in perm's order, plain fp64 adds of a, of |a|, and
+    of 1."""
+    if a.dim() != 3 or a.dtype != torch.float32 or not a.is_contiguous() or min(a.shape) < 1:
+        raise ValueError(f"a must be a contiguous fp32 [rows, k, n] tensor, got {a.dtype} {tuple(a.shape)}")
+    B, k, n = a.shape
+    dev = a.device
+    P, h = _grouped(perm, seg, dev)
+    _dense(sum, torch.float64, (h, n), dev, "sum")
+    _dense(abs_sum, torch.float64, (h, n), dev, "abs_sum")
+    _dense(count, torch.int64, (h,), dev, "count")
+    if sum is None or abs_sum is None or count is None:
+        raise ValueError("sum, abs_sum and count are all needed")
+    check(lib().cc_pairs_latent_sums(_ptr(a), B, k, n, _ptr(perm), P, _ptr(seg), h, _ptr(sum), _ptr(abs_sum),
+                                     _ptr(count), _stream(a)))
+
+
 # ---------------------------------------------------------------- BatchTopK (one selection over the whole batch)
 def batch_topk_part_rows(B, h):
     return int(lib().cc_batch_topk_part_rows(B, h))

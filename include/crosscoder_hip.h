@@ -783,6 +783,61 @@ int cc_resample_write(const void* X, int64_t ldx, int64_t R, const int64_t* rows
                       int64_t h, int64_t K, int dtype, float enc_norm, float dec_norm, void* params, float* master,
                       void* exp_avg, void* exp_avg_sq, int state_dtype, int32_t* done, void* stream);
 
+/* ---- The backward of cc_decode_pairs and the per-latent accumulator of LatentAttribution (CrossCoder.decode_pairs(...,
+ * differentiable=True), pairs_attribution, LatentAttribution).  Gather kernels: no [B][h] or dense [B][h]-sized matrix is
+ * formed.  No float atomics, no spin waits; every summation order is fixed by the arguments alone, so two calls give
+ * the same bits.  K = n * d.
+ *
+ * cc_pairs_grad_values: the sampled dot product of g [B][ldg] (dtype; any [B][K] matrix, in practice the gradient on
+ * the reconstruction) with the decoder rows the pairs name.  idx [B][k] (int32, dense), val [B][k] (dtype, dense,
+ * optional), W_dec [h][ldw] (dtype); dot [B][k][n] and total [B][k] (fp32, dense, each optional, at least one given).
+ *   dot[r][s][m] = sum over c in [m d, (m+1) d) of float(g[r][c]) * float(W_dec[idx[r][s]][c]):  a wave owns the slot;
+ *   lane l folds the model's 8-column groups G (columns 8 G .. 8 G + 7) with G % 64 == l in ascending G, columns in
+ *   order, into one fp32 fma chain from +0; the 64 lane sums are added by the xor butterfly 32, 16, 8, 4, 2, 1.  With
+ *   val, that sum is multiplied once in fp32 by float(val[r][s]): the pair's attribution.
+ *   total[r][s] = +0 + dot[r][s][0] + dot[r][s][1] + ... in model order (the multiplied sums where val is given).
+ * A slot whose index is outside [0, h) (one unsigned compare, as in cc_decode_pairs) gives +0 everywhere and its W_dec row
+ * is not read; duplicate indices are computed independently.  The row of g is read from memory once per token (staged
+ * in LDS; columns past the first 8192 are re-read through the caches).
+ * Errors, checked in this order before any launch: CC_ERR_SHAPE (B, k, h or n < 1, d < 8 or d % 8 != 0, ldw < K,
+ * ldg < K), CC_ERR_NULL (idx, W_dec or g missing, neither output), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h or K > 2^31 - 1,
+ * k > 2^17), CC_ERR_ALIGN (16 bytes: W_dec, g and their row pitches; 4 bytes: idx, dot, total; val: its element).
+ *
+ * The two entry points below take the pairs grouped by latent: perm [P] (int32) holds flat slot numbers r * k + s and
+ * seg [h + 1] (int64) offsets into it: latent j's pairs are perm[seg[j] .. seg[j+1]), in the caller's order (ops.
+ * pairs_by_latent: by (r, s)).  idx is not read: segment j IS latent j.  seg values are clamped to [0, P], a segment
+ * with end < begin is empty, and a perm entry outside [0, B k) is skipped: no input causes an out-of-range access.
+ *
+ * cc_pairs_grad_decoder: dW [h][ldo] (dtype; every row's K columns are written) = pairs^T . g:
+ *   dW[j][c] = dtype(sum over p in [seg[j], seg[j+1]) of float(val[perm[p]]) * float(g[perm[p] / k][c])).
+ *   A segment of at most L = CC_PAIRS_GRAD_SPLIT entries: one fp32 fma chain from +0 in segment order, rounded once.  A
+ *   longer one: its consecutive pieces of L entries (the last piece shorter) are each such a chain from +0, the piece
+ *   sums are added in piece order onto +0 in fp32, and that sum is rounded once; the pieces run in workgroups of
+ *   their own (a latent that fires in every row does not serialise the launch).  An empty segment gives a row of +0.
+ *   ws: cc_pairs_grad_decoder_ws_floats(P, K) = (P / L) * K floats of caller scratch for the full pieces' sums (may
+ *   be NULL where that is 0).  Two launches on `stream`.
+ * Errors in this order: CC_ERR_SHAPE (B, k or h < 1, P < 0, K < 8 or K % 8 != 0, ldg < K, ldo < K), CC_ERR_NULL (seg,
+ * val, g or dW missing, perm missing with P > 0, ws missing with P >= L), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h, K, P or
+ * B * k > 2^31 - 1, k > 2^17), CC_ERR_ALIGN (16 bytes: g, dW, their row pitches, ws; 8: seg; 4: perm; val: its element).
+ *
+ * cc_pairs_latent_sums: a [B k][n] (fp32, dense; cc_pairs_grad_values' dot) folded into the persistent per-latent state
+ * sum [h][n], abs_sum [h][n] (fp64) and count [h] (int64): for latent j and each p of its segment in order,
+ *   sum[j][m] += (double)a[perm[p]][m];  abs_sum[j][m] += fabs((double)a[perm[p]][m]);  count[j] += 1
+ * -- plain fp64 adds onto the stored values, one thread per (j, m): a CPU fp64 loop gives the same bits.
+ * Errors in this order: CC_ERR_SHAPE (B, k, h or n < 1, P < 0), CC_ERR_NULL (a, seg, sum, abs_sum or count missing,
+ * perm missing with P > 0), CC_ERR_TOO_LARGE (h, n, P or B * k > 2^31 - 1, k > 2^17), CC_ERR_ALIGN (8 bytes: seg, sum,
+ * abs_sum, count; 4: a, perm). */
+#define CC_PAIRS_GRAD_SPLIT 128
+int cc_pairs_grad_values(const int32_t* idx, const void* val, int64_t B, int k, const void* W_dec, int64_t ldw,
+                         int64_t h, const void* g, int64_t ldg, int64_t n, int64_t d, int dtype, float* dot,
+                         float* total, void* stream);
+int64_t cc_pairs_grad_decoder_ws_floats(int64_t P, int64_t K);
+int cc_pairs_grad_decoder(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val, int64_t B,
+                          int k, const void* g, int64_t ldg, int64_t K, int dtype, void* dW, int64_t ldo, float* ws,
+                          void* stream);
+int cc_pairs_latent_sums(const float* a, int64_t B, int k, int64_t n, const int32_t* perm, int64_t P,
+                         const int64_t* seg, int64_t h, double* sum, double* abs_sum, int64_t* count, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
