@@ -160,6 +160,13 @@ SIGNATURES = {
     "cc_pairs_grad_decoder_ws_floats": (_i64, [_i64, _i64]),
     "cc_pairs_grad_decoder": (_i, [_p, _i64, _p, _i64, _p, _i64, _i, _p, _i64, _i64, _i, _p, _i64, _p, _p]),
     "cc_pairs_latent_sums": (_i, [_p, _i64, _i, _i64, _p, _i64, _p, _i64, _p, _p, _p, _p]),
+    "cc_pairs_group_ws_bytes": (_i64, [_i64, _i, _i64]),
+    "cc_pairs_group": (_i, [_p, _i64, _i, _i64, _p, _p, _p, _p]),
+    "cc_decode_pairs_partial": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _i64, _i, _p, _i64, _p]),
+    "cc_pairs_wgrad_ws_floats": (_i64, [_i64, _i64]),
+    "cc_pairs_wgrad_parts": (_i64, [_i64]),
+    "cc_pairs_wgrad": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i64, _p, _p,
+                            _p, _p, _p, _p]),
 }
 
 _lib = None

@@ -164,6 +164,20 @@ def master_weights_of(cfg):
     return mw
 
 
+def sparse_step_of(cfg):
+    """cfg["sparse_step"] (framework extension; the key travels in the checkpoint's cfg json): a bool, absent or False:
+    off.  True needs activation "topk": Trainer.step then runs its decode and its whole backward on the k (value,
+    latent) pairs per row instead of the masked dense activations.  It changes Trainer.step
+    only: encode, decode, forward and get_losses are the dense code either way."""
+    sp = cfg.get("sparse_step", False)
+    if not isinstance(sp, bool):
+        raise ValueError(f"cfg['sparse_step'] must be a bool, got {sp!r}")
+    if sp and cfg.get("activation", "relu") != "topk":
+        raise ValueError(f"cfg['sparse_step'] needs activation 'topk' (k pairs per row), got "
+                         f"{cfg.get('activation', 'relu')!r}")
+    return sp
+
+
 class CrossCoder(nn.Module):
     def __init__(self, cfg, n_models: Optional[int] = None, init_W_dec: Optional[torch.Tensor] = None):
         """init_W_dec (framework extension): start from this decoder ([h, n, d], W_enc = its rearranged
@@ -177,6 +191,7 @@ class CrossCoder(nn.Module):
         self.n_models = int(n_models if n_models is not None else cfg.get("n_models", 2))
         self.auxk = auxk_options(cfg, self.n_models)  # (auxk_coeff, k_aux, dead_tokens) or None: Trainer.step's
         master_weights_of(cfg)  # (validated here; Trainer's optimizer is what it switches)
+        sparse_step_of(cfg)  # (validated here; Trainer.step is what it switches)
         self.dtype = DTYPES[cfg["enc_dtype"]]
         if self.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("crosscoder_amd kernels support enc_dtype 'bf16' and 'fp32'")

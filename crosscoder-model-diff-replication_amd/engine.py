@@ -32,6 +32,9 @@ Step (reference trainer.py:41-63 -> crosscoder.py:96-130 -> autograd -> clip -> 
   adam      encoder half on this stream (+ the next batch's prep); the decoder half's first rows on the side
             stream beside the next step's G1 (with the next step's norm partials)   trainer.py:47
 G1, G3 and G4G5 are persistent launches that hand out their tiles per XCD from counters (DYNAMIC_TILES).
+The sparse TopK step (forward_sparse / backward_sparse, a StepWorkspace built with sparse=True; cfg["sparse_step"]) keeps
+prep, G1, the loss kernels and adam, and runs G2 and the whole backward on the selection's k (value, latent) pairs per
+row (csrc/sparse_step.hip, csrc/pairs_grad.hip) instead of G2, G3 and G4G5.
 """
 import contextlib
 
@@ -189,7 +192,7 @@ class StepWorkspace:
     """All activations / partial-sum slabs of one step, allocated once per (B, shape, dtype)."""
 
     def __init__(self, B, n, d, h, dtype, device, transposed=None, topk=None, batch_topk=None, auxk=None,
-                 jumprelu=None):
+                 jumprelu=None, sparse=False):
         """topk (a TopK crosscoder's k): forward() masks G1's activations in place to each row's k largest (one
         cc_topk_rows launch) and the step runs in its batch-major form, whose G3 / G4 read ws.acts itself.
         batch_topk ((k, weighted) of a BatchTopK crosscoder): instead, to the batch's B * k best pairs (cc_batch_topk,
@@ -200,9 +203,16 @@ class StepWorkspace:
         jumprelu (a JumpReLU crosscoder's bandwidth eps): forward() masks G1's activations in place to those above
         their latent's threshold (one cc_jumprelu_mask launch, which also writes ws.gate, G3's mask operand), in the
         batch-major form; the workspace owns the gate, the backward pass' two slabs (the threshold gradient's partials
-        and g_pre's recomputed column partials) and a fifth segment of ws.sq for the threshold's squared gradient."""
+        and g_pre's recomputed column partials) and a fifth segment of ws.sq for the threshold's squared gradient.
+        sparse (with topk, the Trainer's sparse step: forward_sparse / backward_sparse): the workspace owns the pairs
+        (pair_idx, pair_val), their d_acts (pair_gpre, fp32), perm / seg and the grouping's and the list gradients'
+        scratch; it allocates no g_pre, no g_pre column partials and no G2 split-K workspace, and the first three
+        segments of ws.sq take cc_pairs_wgrad's partials."""
         f32 = torch.float32
         self.topk = topk
+        self.sparse = bool(sparse)
+        if self.sparse and (topk is None or auxk is not None):
+            raise ValueError("a sparse workspace needs topk and excludes auxk")
         self.batch_topk, self.bt_weighted = batch_topk if batch_topk is not None else (None, False)
         if topk is not None and batch_topk is not None:
             raise ValueError("topk and batch_topk exclude each other")
@@ -281,7 +291,7 @@ class StepWorkspace:
         self.l1_part = E(self.n_l1)  # per 64-latent block: sum_h colsum_acts[h] * tn[h] (= B * l1)
         self.recon_full = E(R, K)
         self.recon = self.recon_full[:B]
-        nws = ops.decode_ws_floats(B, h, K, dtype)
+        nws = 0 if self.sparse else ops.decode_ws_floats(B, h, K, dtype)
         self.dec_ws = E(nws) if nws else None  # G2 split-K partials
         self.g_recon_full = E(R, K, dt=dtype)
         self.g_recon = self.g_recon_full[:B]
@@ -302,11 +312,21 @@ class StepWorkspace:
         self.scalars = E(ops.loss_scalars_len(B))
         # transposed mode stores g_pre only as g_pre_t [h][B]; ws.g_pre is then its [B][h] view
         self.g_pre_t = E(h, B, dt=dtype) if self.tr else None
-        self.g_pre_full = None if self.tr else E(R, h, dt=dtype)
-        self.g_pre = self.g_pre_t.t() if self.tr else self.g_pre_full[:B]
+        self.g_pre_full = None if self.tr or self.sparse else E(R, h, dt=dtype)
+        self.g_pre = self.g_pre_t.t() if self.tr else self.g_pre_full[:B] if not self.sparse else None
         cpr = ops.col_part_rows(B)
-        self.gpre_colpart_full = E(cpr * (R // B), h)
-        self.gpre_colpart = self.gpre_colpart_full[:cpr]
+        self.gpre_colpart_full = None if self.sparse else E(cpr * (R // B), h)
+        self.gpre_colpart = None if self.sparse else self.gpre_colpart_full[:cpr]
+        if self.sparse:
+            k = int(topk)
+            self.pair_idx = E(B, k, dt=torch.int32)
+            self.pair_val = E(B, k, dt=dtype)
+            self.pair_gpre = E(B, k)  # d_acts at the pairs, fp32: the list gradients round it where they read it
+            self.perm = E(B * k, dt=torch.int32)
+            self.seg = E(h + 1, dt=torch.int64)
+            self.group_ws = E(ops.pairs_group_ws_bytes(B, k, h), dt=torch.uint8)
+            nwg = ops.pairs_wgrad_ws_floats(B * k, K)
+            self.wgrad_ws = E(nwg) if nwg else None
         if auxk is not None:
             # the aux halves, and the aux loss's partial slabs, scalars {auxk_loss, den, scale, valid}, the rows'
             # selected counts, the dead mask the step's selection used and the dead count after the step
@@ -321,6 +341,8 @@ class StepWorkspace:
         nw_w = ops.wgrad_parts(h, K, dtype)
         self.inv_norms = E(h, n)
         sizes = [nw_w, nw_w, ops.reduce_parts(h), ops.reduce_parts(K)]
+        if self.sparse:
+            sizes[:3] = [ops.pairs_wgrad_parts(h)] * 3
         if jumprelu is not None:
             sizes.append(ops.reduce_parts(h))  # the thresholds' gradient
         self.sq_off = [0]
@@ -532,6 +554,55 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
         loss_rows(ws, P, 0, ws.B, grad_scale)
         if finalize:
             loss_finalize(ws)
+
+
+def forward_sparse(ws, P, x_in, factor=None, prep_tag=None):
+    """forward(finalize=False) of the sparse TopK step (a workspace built with sparse=True): prep
+    and G1 as the dense TopK step, then the selection as k (value, latent) pairs per row with the same column-sum and
+    count slabs (no dense masked write: ws.acts keeps G1's activations), the pairs grouped by latent (ws.perm, ws.seg),
+    the plain event wait for the decoder-half Adam, the sparse G2 into ws.recon and the loss rows.  The caller forks
+    the loss tail (loss_finalize_beside, or loss_finalize on this stream)."""
+    B, h, K = ws.B, ws.h, ws.K
+    ws.next_slot()
+    prepped, ws.prep_token = ws.prep_token, None
+    if prepped is not None and prepped == _prep_token(x_in, factor, prep_tag):
+        (ws.x, ws.x_t, ws.x_colpart), ws.x_next = ws.x_next, (ws.x, ws.x_t, ws.x_colpart)
+    else:
+        with _span("prep"):
+            ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
+    with _span("G1_encode"):
+        ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True)
+    with _span("topk_pairs"):
+        ops.topk_rows(ws.acts, h, ws.topk, out=None, idx_out=ws.pair_idx, val_out=ws.pair_val,
+                      colsum_part=ws.acts_colpart, l0_part=ws.l0_part)
+    with _span("pairs_group"):
+        ops.pairs_group(ws.pair_idx, h, perm=ws.perm, seg=ws.seg, ws=ws.group_ws)
+    ops.reduce_rows(ws.x_colpart, ws.x_colpart.shape[0], K, scale=1.0 / B, out_f32=ws.x_mean)
+    ops.reduce_rows(ws.acts_colpart, ws.acts_colpart.shape[0], h, out_f32=ws.colsum_acts)
+    P.wait_pending()
+    decoder_norms(ws, P)
+    with _span("G2_decode_pairs"):
+        ops.decode_pairs_partial(ws.pair_val, ws.pair_idx, P.W_dec_hk, K, h=h, recon=ws.recon)
+    flush_norms(ws)
+    ws.acts_pending = True
+    loss_rows(ws, P, 0, B)
+
+
+def backward_sparse(ws, P, G):
+    """The sparse TopK step's backward, for l2 alone (l1_coeff = 0): d_acts at the pairs (the sampled dot products of
+    g_recon with the selected decoder rows; a selected activation is > 0, so the straight-through mask is 1), the three
+    list gradients with their squared-sum partials in one grouped launch pair, and b_dec's gradient from the loss's
+    column partials.  clip_and_adam then runs its clip_finalize over ws.sq."""
+    P.wait_pending()
+    with _span("pairs_dacts"):
+        ops.pairs_grad_values(ws.pair_idx, P.W_dec_hk, ws.g_recon, ws.n, ws.d, h=ws.h, total=ws.pair_gpre,
+                              want_dot=False)
+    with _span("pairs_wgrad"):
+        ops.pairs_wgrad(ws.perm, ws.seg, ws.pair_val, ws.pair_gpre, ws.g_recon, ws.x, ws.K, G.W_dec_hk, G.W_enc_hk,
+                        G.b_enc, ws.sq_slice(1), ws.sq_slice(0), ws.sq_slice(2), ws=ws.wgrad_ws)
+    with _span("b_dec_grad"):
+        ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, ws.K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
+    ws.clip_ready = False
 
 
 STEP_ABORTED_MSG = ("crosscoder_hip: the step was aborted -- G2's in-kernel wait for the previous step's decoder-half "

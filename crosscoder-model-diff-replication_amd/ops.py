@@ -981,6 +981,109 @@ def pairs_latent_sums(a, perm, seg, sum, abs_sum, count):
                                      _ptr(count), _stream(a)))
 
 
+# ---------------------------------------------------------------- the sparse TopK step's kernels (sparse_step.hip)
+def pairs_group_ws_bytes(B, k, h):
+    return int(lib().cc_pairs_group_ws_bytes(B, k, h))
+
+
+def pairs_group(idx, h, perm=None, seg=None, ws=None):
+    """pairs_by_latent as one kernel sequence in stream order (cc_pairs_group): idx [B, k] int32, contiguous -> (perm
+    int32 [B k], seg int64 [h + 1]); seg and perm[:seg[h]] equal pairs_by_latent's, the rest of perm is unspecified
+    inside [0, B k).  ws: uint8, at least pairs_group_ws_bytes(B, k, h) bytes, 16-byte aligned (allocated when None)."""
+    B, k = _pairs_idx(idx, None)
+    dev = idx.device
+    if isinstance(h, bool) or not isinstance(h, int) or h < 1:
+        raise ValueError(f"h must be an int >= 1, got {h!r}")
+    _dense(perm, torch.int32, (B * k,), dev, "perm")
+    _dense(seg, torch.int64, (h + 1,), dev, "seg")
+    need = pairs_group_ws_bytes(B, k, h)
+    if need == 0:
+        raise ValueError(f"pairs_group: (rows, k, h) = ({B}, {k}, {h}) is out of the kernel's range")
+    if ws is not None and (ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"ws must be a contiguous uint8 tensor of at least {need} elements on {dev}")
+    stream = _stream(idx)
+    if perm is None:
+        perm = torch.empty(B * k, dtype=torch.int32, device=dev)
+    if seg is None:
+        seg = torch.empty(h + 1, dtype=torch.int64, device=dev)
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(lib().cc_pairs_group(_ptr(idx), B, k, h, _ptr(perm), _ptr(seg), _ptr(ws), stream))
+    return perm, seg
+
+
+def decode_pairs_partial(val, idx, W_dec, K, h=None, recon=None):
+    """The fp32 partial reconstruction of k (value, latent) pairs per row (cc_decode_pairs_partial): recon fp32 [B, >= K]
+    <- the fp32 fma chain +0 + sum_s val[r, s] * W_dec[idx[r, s], c] over the slots in order -- decode_pairs' chain
+    without the bias and the rounding, what decode_partial hands to loss_fwd_bwd.  val [B, k] (bf16 / fp32) and idx
+    int32, contiguous; W_dec [>= h, >= K] of val's dtype (column slices keep their pitch)."""
+    B, k = _pairs_idx(idx, val)
+    dt, dev = val.dtype, val.device
+    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
+        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
+    if W_dec.dim() != 2 or W_dec.shape[1] < K or W_dec.dtype != dt or W_dec.device != dev:
+        raise ValueError(f"W_dec must be [h, >= {K}] of {dt} on {dev}, got {W_dec.dtype} {tuple(W_dec.shape)}")
+    h = W_dec.shape[0] if h is None else h
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
+        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
+    if recon is not None and (recon.dim() != 2 or recon.shape[0] != B or recon.shape[1] < K
+                              or recon.dtype != torch.float32 or recon.device != dev):
+        raise ValueError(f"recon must be fp32 [{B}, >= {K}] on {dev}, got {recon.dtype} {tuple(recon.shape)}")
+    pw, ldw = _pitched(W_dec, K, "W_dec")
+    stream = _stream(val)
+    if recon is None:
+        recon = torch.empty(B, K, dtype=torch.float32, device=dev)
+    pr, ldr = _pitched(recon, K, "recon")
+    check(lib().cc_decode_pairs_partial(_ptr(val), _ptr(idx), B, k, pw, ldw, h, K, dtype_code(dt), pr, ldr, stream))
+    return recon
+
+
+def pairs_wgrad_ws_floats(P, K):
+    return int(lib().cc_pairs_wgrad_ws_floats(P, K))
+
+
+def pairs_wgrad_parts(h):
+    return int(lib().cc_pairs_wgrad_parts(h))
+
+
+def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq_dec, sq_enc, sq_b_enc, ws=None):
+    """The sparse step's weight gradients from the pairs grouped by latent (cc_pairs_wgrad): per latent j and its list
+    in perm's order, dW_dec[j] = sum val * g_recon[row], dW_enc[j] = sum p * x[row], db_enc[j] = sum p with p = g_pre
+    rounded to the dtype -- pairs_grad_decoder's order for all three, rounded once -- plus the squared sums of the
+    stored values, pairs_wgrad_parts(h) fp32 partials per parameter.  val [B, k] (bf16 / fp32) and g_pre fp32 [B, k],
+    contiguous; g_recon, x [B, >= K] and dW_dec, dW_enc [h, >= K] of val's dtype (pitches kept); db_enc [h] of it; ws:
+    fp32, at least pairs_wgrad_ws_floats(len(perm), K) elements (allocated when None)."""
+    if val.dim() != 2 or val.shape[0] < 1 or val.shape[1] < 1 or val.dtype not in _DT or not val.is_contiguous():
+        raise ValueError(f"val must be a contiguous bf16 or fp32 [rows >= 1, k >= 1] tensor, got {val.dtype} "
+                         f"{tuple(val.shape)}")
+    B, k = val.shape
+    dt, dev = val.dtype, val.device
+    P, h = _grouped(perm, seg, dev)
+    _dense(g_pre, torch.float32, (B, k), dev, "g_pre")
+    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
+        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
+    for name, t, rows in (("g_recon", g_recon, B), ("x", x, B), ("dW_dec", dW_dec, h), ("dW_enc", dW_enc, h)):
+        if t is None or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < K or t.dtype != dt or t.device != dev:
+            raise ValueError(f"{name} must be [{rows}, >= {K}] of {dt} on {dev}")
+    _dense(db_enc, dt, (h,), dev, "db_enc")
+    parts = pairs_wgrad_parts(h)
+    for name, t in (("sq_dec", sq_dec), ("sq_enc", sq_enc), ("sq_b_enc", sq_b_enc)):
+        _dense(t, torch.float32, (parts,), dev, name)
+    if g_pre is None or db_enc is None or sq_dec is None or sq_enc is None or sq_b_enc is None:
+        raise ValueError("g_pre, db_enc and the three sq partials are all needed")
+    need = (P // PAIRS_GRAD_SPLIT) * (2 * K + 8)
+    if ws is not None and (ws.dtype != torch.float32 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"ws must be a contiguous fp32 tensor of at least {need} elements on {dev}")
+    (pg, ldg), (px, ldx) = _pitched(g_recon, K, "g_recon"), _pitched(x, K, "x")
+    (pd, ldd), (pe, lde) = _pitched(dW_dec, K, "dW_dec"), _pitched(dW_enc, K, "dW_enc")
+    stream = _stream(val)
+    if ws is None and need:
+        ws = torch.empty(pairs_wgrad_ws_floats(P, K), dtype=torch.float32, device=dev)
+    check(lib().cc_pairs_wgrad(_ptr(perm), P, _ptr(seg), h, _ptr(val), _ptr(g_pre), B, k, pg, ldg, px, ldx, K,
+                               dtype_code(dt), pd, ldd, pe, lde, _ptr(db_enc), _ptr(sq_dec), _ptr(sq_enc),
+                               _ptr(sq_b_enc), _ptr(ws), stream))
+
+
 # ---------------------------------------------------------------- BatchTopK (one selection over the whole batch)
 def batch_topk_part_rows(B, h):
     return int(lib().cc_batch_topk_part_rows(B, h))

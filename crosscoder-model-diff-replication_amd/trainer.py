@@ -11,13 +11,15 @@ fp32 moments instead, the bf16 parameters being the masters rounded after every 
 `Trainer.state_dict()` / `load_state_dict()` carry the optimizer's state across a restart in either mode.
 cfg["resample_every"] = N re-seeds the dead latents after every N-th step (dead-latent resampling, DESIGN.md section
 3.18; `Trainer.resample_dead_latents` is the same between steps of the caller's choosing).
+cfg["sparse_step"] = True (TopK crosscoders, l1_coeff 0) runs the step's decode and backward on the k (value, latent)
+pairs per row instead of the masked dense activations; `Trainer.sparse_step` says which ran.
 """
 import torch
 import tqdm
 
 from . import _hip, engine
 from .buffer import Buffer
-from .crosscoder import CrossCoder, master_weights_of
+from .crosscoder import CrossCoder, master_weights_of, sparse_step_of
 from .resample import LatentResampler
 
 RESAMPLE_ROWS = 819200  # cfg["resample_rows"]'s default: the pool of "Towards Monosemanticity"'s neuron resampling
@@ -253,6 +255,22 @@ class Trainer:
         # periodic dead-latent resampling (resample_options); the pool is allocated with the first resample
         self.resample = resample_options(cfg)
         self._resampler = None
+        # the sparse TopK step (crosscoder.sparse_step_of): what it does not serve is refused here, not run densely
+        self.sparse_step = sparse_step_of(cfg)
+        self._sparse_ws = None  # its workspace, the Trainer's own: the crosscoder's serves get_losses' dense autograd
+        if self.sparse_step:
+            why = None
+            if cfg["l1_coeff"] != 0:
+                why = ("cfg['l1_coeff'] != 0: TopK replaces the L1 penalty, and the L1 term's dense dW_dec part is not "
+                       "built for the sparse step")
+            elif self.auxk is not None:
+                why = "cfg['auxk_coeff'] > 0: the AuxK loss on pairs is not built"
+            elif self.resample is not None:
+                why = "cfg['resample_every']: resampling under the sparse step is not built"
+            elif latent_stats is not None:
+                why = "latent_stats=...: the sparse step never writes the masked dense activations"
+            if why is not None:
+                raise ValueError(f"cfg['sparse_step'] is not served with {why}")
 
     def lr_lambda(self, step):
         if step < 0.8 * self.total_steps:
@@ -331,10 +349,13 @@ class Trainer:
         # the buffer's refresh count tags the batch for engine.PREP_IN_ADAM: the last step's Adam launch may have
         # prepped exactly these rows
         tag = getattr(self.buffer, "refresh_count", 0)
-        ws = cc._workspace(raw.shape[0], step=True)
         P = cc.arena()
         opt = self.optimizer
         side = self._side_stream()
+        if self.sparse_step:
+            ws = self._launch_sparse_step(raw, factor if normalize else None, tag, P, side, host, seq)
+            return self._launch_adam(ws, P, side, normalize, self.get_l1_coeff(), None, False)
+        ws = cc._workspace(raw.shape[0], step=True)
         # prep, G1, G2 + the loss rows (one pass where decode_loss_t serves the shape)
         # (BatchTopK: the selection's last launch folds the step's threshold score T into the crosscoder's inference
         # threshold -- T at the first step, then beta * threshold + (1 - beta) * T -- on the device, in stream order)
@@ -365,6 +386,12 @@ class Trainer:
             engine.backward_auxk(ws, P, opt.grads, l1c, clip=1.0)
         else:
             engine.backward(ws, P, opt.grads, l1c, clip=1.0)
+        self._launch_adam(ws, P, side, normalize, l1c, l0c, aux_on)
+
+    def _launch_adam(self, ws, P, side, normalize, l1c, l0c, aux_on):
+        """The end of every step's launches: clip_grad_norm_'s coefficient (where the backward did not leave it) and
+        Adam, then the step's bookkeeping."""
+        cc, opt = self.crosscoder, self.optimizer
         g = opt.param_groups[0]
         opt.t += 1
         b1, b2 = g["betas"]
@@ -386,6 +413,23 @@ class Trainer:
         self._last_l0c = l0c
         self._last_ws = ws
         self._last_aux_on = aux_on
+
+    def _sparse_workspace(self, B, P):
+        cc, ws = self.crosscoder, self._sparse_ws
+        if ws is None or ws.B != B or ws.x.device != P.data.device:
+            ws = self._sparse_ws = engine.StepWorkspace(B, cc.n_models, cc._dp, cc._hp, cc.dtype, P.data.device,
+                                                        topk=cc.k, sparse=True)
+        return ws
+
+    def _launch_sparse_step(self, raw, factor, tag, P, side, host, seq):
+        """_launch_step's forward and backward for cfg["sparse_step"] (engine.forward_sparse / backward_sparse): no launch
+        of it waits in its kernel, so the step has no abort word, and the loss tail runs beside d_acts on the side
+        stream.  -> the workspace, for _launch_adam."""
+        ws = self._sparse_workspace(raw.shape[0], P)
+        engine.forward_sparse(ws, P, raw, factor, prep_tag=tag)
+        engine.loss_finalize_beside(ws, side, host=host, seq=seq)
+        engine.backward_sparse(ws, P, self.optimizer.grads)
+        return ws
 
     def _side_stream(self):
         # the decoder half of Adam (+ the next step's decoder norms / W_dec^T) runs here, beside the

@@ -838,6 +838,61 @@ int cc_pairs_grad_decoder(const int32_t* perm, int64_t P, const int64_t* seg, in
 int cc_pairs_latent_sums(const float* a, int64_t B, int k, int64_t n, const int32_t* perm, int64_t P,
                          const int64_t* seg, int64_t h, double* sum, double* abs_sum, int64_t* count, void* stream);
 
+/* ---- The sparse TopK training step's own kernels (Trainer.step with cfg["sparse_step"]), beside
+ * cc_topk_rows' pairs, cc_pairs_grad_values and the loss kernels.  No float atomics, no spin waits, no host reads; every
+ * float summation order is fixed by the arguments alone, so two calls give the same bits.
+ *
+ * cc_pairs_group: the pairs idx [B][k] (int32, dense; a slot whose index is outside [0, h) is padding) grouped by latent:
+ * seg [h + 1] (int64) and perm [B k] (int32) such that perm[seg[j] .. seg[j+1]) are the flat slot numbers r * k + s of
+ * latent j's pairs in ascending order, i.e. the valid slots sorted by (latent, row, slot) -- ops.pairs_by_latent's seg
+ * and perm[:seg[h]].  Entries of perm from seg[h] on are unspecified values inside [0, B k).  A counting sort over
+ * (latent, 256-row block) cells: integer atomics count and place, and a rank by slot number inside each cell removes
+ * their arrival order; a latent that fires in every row is ceil(B / 256) cells ranked by their own threads.
+ * ws: cc_pairs_group_ws_bytes(B, k, h) bytes of caller scratch (0: the arguments are out of range).  A memset and five
+ * launches on `stream`.
+ * Errors in this order: CC_ERR_SHAPE (B, k or h < 1), CC_ERR_NULL, CC_ERR_TOO_LARGE (h or B * k > 2^31 - 1, k > 2^17,
+ * h * ceil(B / 256) > 2^28), CC_ERR_ALIGN (16 bytes: ws; 8: seg; 4: idx, perm).
+ *
+ * cc_decode_pairs_partial: recon [B][ldr] (fp32; the K columns of every row are written) = the fp32 fma chain
+ *   +0 + sum_s float(val[r][s]) * float(W_dec[idx[r][s]][c])   over the slots s = 0 .. k-1 in that order,
+ * cc_decode_pairs' chain from +0 instead of b_dec[c] and without the rounding: the partial reconstruction the dense
+ * cc_decode_partial hands to cc_loss_fwd_bwd.  A slot whose index is outside [0, h) adds nothing and reads nothing.
+ * Errors in this order: CC_ERR_SHAPE (B, k or h < 1, K < 8 or K % 8 != 0, ldw < K, ldr < K), CC_ERR_NULL, CC_ERR_DTYPE,
+ * CC_ERR_TOO_LARGE (h or K > 2^31 - 1, k > 2^17), CC_ERR_ALIGN (16 bytes: W_dec, recon and their row pitches; 4: idx;
+ * val: its element).
+ *
+ * cc_pairs_wgrad: the step's three list gradients from one walk of the pairs grouped by latent (perm [P], seg [h + 1]:
+ * the two entry points above this block describe them; the same clamping, so garbage gives garbage sums in bounds):
+ *   dW_dec[j][c] = dtype(sum over latent j's list of float(val[slot]) * float(g_recon[slot / k][c]))
+ *   dW_enc[j][c] = dtype(sum over latent j's list of p(slot) * float(x[slot / k][c]))
+ *   db_enc[j]    = dtype(sum over latent j's list of p(slot))          p(slot) = float(dtype(g_pre[slot]))
+ * val [B][k] (dtype, dense), g_pre [B][k] (fp32, dense: cc_pairs_grad_values' total, rounded to the dtype where it is
+ * read), g_recon [B][ldg] and x [B][ldx] (dtype), dW_dec [h][ld_dec], dW_enc [h][ld_enc] (dtype; every row's K columns
+ * are written), db_enc [h] (dtype).  Order: exactly cc_pairs_grad_decoder's -- a list of at most L =
+ * CC_PAIRS_GRAD_SPLIT entries is one fp32 chain from +0 in list order (fma for the two matrices, a plain add for
+ * db_enc), rounded once; a longer list in consecutive pieces of L, the piece sums added in piece order onto +0, rounded
+ * once.  An empty list gives +0.  sq_dec, sq_enc, sq_b_enc: cc_pairs_wgrad_parts(h) floats each, the squared sums of
+ * the stored (rounded) values: a lane's fma(r, r, sq) chain over the elements it stores in the order it stores them
+ * (rows j = g, g + parts, ...; per row its 8-column groups t, t + 256, ...), the xor butterfly 32 .. 1, the four waves
+ * in order; one partial per workgroup g at index g.
+ * ws: cc_pairs_wgrad_ws_floats(P, K) = (P / L) * (2 K + 8) floats of caller scratch (may be NULL where that is 0).
+ * Two launches on `stream`.
+ * Errors in this order: CC_ERR_SHAPE (B, k or h < 1, P < 0, K < 8 or K % 8 != 0, a row pitch < K), CC_ERR_NULL (any
+ * operand missing; perm with P > 0, ws with P >= L), CC_ERR_DTYPE, CC_ERR_TOO_LARGE (h, K, P or B * k > 2^31 - 1,
+ * k > 2^17), CC_ERR_ALIGN (16 bytes: g_recon, x, dW_dec, dW_enc, their row pitches, ws; 8: seg; 4: perm, g_pre, the sq
+ * partials; val, db_enc: their element). */
+int64_t cc_pairs_group_ws_bytes(int64_t B, int k, int64_t h);
+int cc_pairs_group(const int32_t* idx, int64_t B, int k, int64_t h, int32_t* perm, int64_t* seg, void* ws,
+                   void* stream);
+int cc_decode_pairs_partial(const void* val, const int32_t* idx, int64_t B, int k, const void* W_dec, int64_t ldw,
+                            int64_t h, int64_t K, int dtype, float* recon, int64_t ldr, void* stream);
+int64_t cc_pairs_wgrad_ws_floats(int64_t P, int64_t K);
+int64_t cc_pairs_wgrad_parts(int64_t h);
+int cc_pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val, const float* g_pre,
+                   int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx, int64_t K, int dtype,
+                   void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc, float* sq_dec,
+                   float* sq_enc, float* sq_b_enc, float* ws, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
