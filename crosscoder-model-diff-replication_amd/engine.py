@@ -442,6 +442,17 @@ def decoder_norms(ws, P):
     _decoder_derived(ws, P)
 
 
+def _take_or_prep(ws, x_in, factor, prep_tag):
+    """ws.x / x_t / x_colpart <- the prepped batch: the one the last Adam launch carried where that was exactly this
+    batch's (PREP_IN_ADAM; the buffers are swapped in), else a prep launch"""
+    prepped, ws.prep_token = ws.prep_token, None
+    if prepped is not None and prepped == _prep_token(x_in, factor, prep_tag):
+        (ws.x, ws.x_t, ws.x_colpart), ws.x_next = ws.x_next, (ws.x, ws.x_t, ws.x_colpart)
+    else:
+        with _span("prep"):
+            ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
+
+
 def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True, finalize=True, bt_threshold=None,
             aux=None, theta=None, prep_tag=None):
     """Forward + reconstruction-loss gradient.  P: params Arena.  x_in [B, n, d] any of
@@ -456,13 +467,7 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
     prep_tag: the tag of adam's next_batch, where x_in may be that batch (the Trainer's: its buffer's refresh count)."""
     B, n, d, h, K = ws.B, ws.n, ws.d, ws.h, ws.K
     ws.next_slot()
-    # (the last Adam launch may have carried exactly this batch's prep: PREP_IN_ADAM)
-    prepped, ws.prep_token = ws.prep_token, None
-    if prepped is not None and prepped == _prep_token(x_in, factor, prep_tag):
-        (ws.x, ws.x_t, ws.x_colpart), ws.x_next = ws.x_next, (ws.x, ws.x_t, ws.x_colpart)
-    else:
-        with _span("prep"):
-            ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
+    _take_or_prep(ws, x_in, factor, prep_tag)
     # G1 reads only the encoder half: it may overlap the previous step's decoder-half Adam.  x.mean(0) (first
     # read by the loss) and sum_b acts (G4's L1 term and the l1 loss, crosscoder.py:112,126): column reductions
     # of the prep / G1 partial slabs -- carried in the prologues of G1 and G2 where the step's fused path runs
@@ -564,12 +569,7 @@ def forward_sparse(ws, P, x_in, factor=None, prep_tag=None):
     the loss tail (loss_finalize_beside, or loss_finalize on this stream)."""
     B, h, K = ws.B, ws.h, ws.K
     ws.next_slot()
-    prepped, ws.prep_token = ws.prep_token, None
-    if prepped is not None and prepped == _prep_token(x_in, factor, prep_tag):
-        (ws.x, ws.x_t, ws.x_colpart), ws.x_next = ws.x_next, (ws.x, ws.x_t, ws.x_colpart)
-    else:
-        with _span("prep"):
-            ops.prep_input(x_in, factor, ws.dtype, out=ws.x, colsum_part=ws.x_colpart, out_t=ws.x_t)
+    _take_or_prep(ws, x_in, factor, prep_tag)
     with _span("G1_encode"):
         ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True)
     with _span("topk_pairs"):

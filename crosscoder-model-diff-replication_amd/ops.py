@@ -663,10 +663,7 @@ def latent_stats_update(acts, h, k, count, sum_, hist, topk_val, topk_row, row_i
     count [h] int64, sum_ [h] fp32, hist [h, 32] int64 or None, topk_val [h, k] fp32, topk_row [h, k] int64
     (cc_latent_stats_update; fresh state: zeros, topk_row -1).  Row b has id row_ids[b] (int64 [B] on the
     device) or row0 + b."""
-    if acts.dim() != 2 or acts.stride(1) != 1:
-        raise ValueError("acts must be [rows, width] with contiguous rows")
-    # (a one-row view may carry any stride: keep it where it is a row pitch)
-    B, ld = acts.shape[0], acts.stride(0) if acts.stride(0) >= acts.shape[1] else acts.shape[1]
+    B, ld = _rows_ld(acts, "acts")
     dev = acts.device
     for name, t, dt, shape in (("count", count, torch.int64, (h,)), ("sum", sum_, torch.float32, (h,)),
                                ("hist", hist, torch.int64, (h, 32)), ("topk_val", topk_val, torch.float32, (h, k)),
@@ -691,6 +688,47 @@ def _pitched(t, cols, name):
     if t.dim() != 2 or t.shape[1] < cols or (t.shape[1] > 1 and t.stride(1) != 1):
         raise ValueError(f"{name} must be [rows, >= {cols}] with contiguous rows, got {tuple(t.shape)}")
     return _ptr(t), t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _int_at_least(v, name, least=1):
+    """a Python int (not a bool) >= least"""
+    if isinstance(v, bool) or not isinstance(v, int) or v < least:
+        raise ValueError(f"{name} must be an int >= {least}, got {v!r}")
+    return v
+
+
+def _mult8(v, name):
+    """a Python int (not a bool), a multiple of 8, >= 8"""
+    if isinstance(v, bool) or not isinstance(v, int) or v < 8 or v % 8:
+        raise ValueError(f"{name} must be an int multiple of 8, got {v!r}")
+    return v
+
+
+def _rows(t, rows, K, dt, dev, name, optional=False):
+    """(pointer, row pitch) of the operand t [rows, >= K] of dt on dev (_pitched: a column slice keeps its pitch);
+    optional: (None, 0) for None"""
+    if t is None and optional:
+        return None, 0
+    if t is None or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < K or t.dtype != dt or t.device != dev:
+        raise ValueError(f"{name} must be [{rows}, >= {K}] of {dt} on {dev}"
+                         + ("" if t is None else f", got {t.dtype} {tuple(t.shape)}"))
+    return _pitched(t, K, name)
+
+
+def _decoder(W_dec, K, dt, dev, h):
+    """(pointer, row pitch, h) of the decoder operand W_dec [>= h, >= K] of dt on dev; h defaults to W_dec's rows"""
+    if W_dec.dim() != 2 or W_dec.shape[1] < K or W_dec.dtype != dt or W_dec.device != dev:
+        raise ValueError(f"W_dec must be [h, >= {K}] of {dt} on {dev}, got {W_dec.dtype} {tuple(W_dec.shape)}")
+    h = W_dec.shape[0] if h is None else h
+    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
+        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
+    return (*_pitched(W_dec, K, "W_dec"), h)
+
+
+def _scratch(ws, dt, need, dev, name="ws"):
+    """an optional contiguous scratch buffer of dt with at least `need` elements on dev"""
+    if ws is not None and (ws.dtype != dt or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
+        raise ValueError(f"{name} must be a contiguous {dt} tensor of at least {need} elements on {dev}")
 
 
 def latent_scaling(Y, W, acts, dot_part, sq_part=None):
@@ -728,8 +766,7 @@ def decoder_match(Wc, Wq, c_scale, q_scale, key_part, row0=0, exclude_diag=False
     N = Wq.shape[0]
     if Wq.shape[1] != K or Wc.dtype != Wq.dtype or Wc.device != Wq.device:
         raise ValueError("decoder_match: Wc [M, K] and Wq [N, K] of one dtype on one device")
-    if isinstance(row0, bool) or not isinstance(row0, int) or row0 < 0:
-        raise ValueError(f"row0 must be an int >= 0, got {row0!r}")
+    _int_at_least(row0, "row0", 0)
     for name, t, least in (("c_scale", c_scale, row0 + M), ("q_scale", q_scale, N)):
         if (t.dtype != torch.float32 or t.dim() != 1 or not t.is_contiguous() or t.device != Wc.device
                 or (t.shape[0] < least if name == "c_scale" else t.shape[0] != least)):
@@ -791,44 +828,24 @@ def decode_pairs(val, idx, W_dec, b_dec, n, d, h=None, recon=None, x=None, sq_er
     kept); sq_err fp32 [B, n]: per row and model, the squared error of the rounded reconstruction against x.
     Without x: writes (and returns) recon, allocated if not given.  With x: writes sq_err (allocated if not given),
     and recon only if given.  -> (recon or None, sq_err or None)."""
-    if val.dim() != 2 or idx.dim() != 2 or val.shape != idx.shape or val.shape[0] < 1 or val.shape[1] < 1:
-        raise ValueError(f"val and idx must both be [rows >= 1, k >= 1], got {tuple(val.shape)} and {tuple(idx.shape)}")
-    if val.dtype not in _DT:
-        raise ValueError(f"val must be bf16 or fp32, got {val.dtype}")
-    if idx.dtype != torch.int32:
-        raise ValueError(f"idx must be int32, got {idx.dtype}")
-    if not val.is_contiguous() or not idx.is_contiguous():
-        raise ValueError("val and idx must be contiguous")
-    for name, v in (("n", n), ("d", d)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
-    if d % 8:
-        raise ValueError(f"d must be a multiple of 8, got {d}")
-    B, k = val.shape
+    B, k = _pairs_idx(idx, val)
+    _int_at_least(n, "n")
+    _mult8(d, "d")
     K, dt, dev = n * d, val.dtype, val.device
-    if W_dec.dim() != 2 or W_dec.shape[1] < K:
-        raise ValueError(f"W_dec must be [h, >= {K}], got {tuple(W_dec.shape)}")
-    h = W_dec.shape[0] if h is None else h
-    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
-        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
+    pw, ldw, h = _decoder(W_dec, K, dt, dev, h)
     _dense(b_dec, dt, (K,), dev, "b_dec")
     if sq_err is not None and x is None:
         raise ValueError("sq_err needs x")
     _dense(sq_err, torch.float32, (B, n), dev, "sq_err")
-    for name, t in (("W_dec", W_dec), ("recon", recon), ("x", x), ("idx", idx)):
-        if t is not None and (t.device != dev or (name != "idx" and t.dtype != dt)):
-            raise ValueError(f"{name} must be on {dev}" + ("" if name == "idx" else f" with dtype {dt}"))
-    for name, t in (("recon", recon), ("x", x)):
-        if t is not None and (t.dim() != 2 or t.shape[0] != B):
-            raise ValueError(f"{name} must be [{B}, >= {K}], got {tuple(t.shape)}")
-    pw, ldw = _pitched(W_dec, K, "W_dec")
+    (pr, ldr), (px, ldx) = _rows(recon, B, K, dt, dev, "recon", True), _rows(x, B, K, dt, dev, "x", True)
+    stream = _stream(val)
     if x is None and recon is None:
         recon = torch.empty(B, K, dtype=dt, device=dev)
+        pr, ldr = _ptr(recon), K
     if x is not None and sq_err is None:
         sq_err = torch.empty(B, n, dtype=torch.float32, device=dev)
-    (pr, ldr), (px, ldx) = ((None, 0) if t is None else _pitched(t, K, name) for name, t in (("recon", recon), ("x", x)))
     check(lib().cc_decode_pairs(_ptr(val), _ptr(idx), B, k, pw, ldw, h, _ptr(b_dec), n, d, dtype_code(dt), pr, ldr,
-                                px, ldx, _ptr(sq_err), _stream(val)))
+                                px, ldx, _ptr(sq_err), stream))
     return recon, sq_err
 
 
@@ -852,6 +869,14 @@ def _pairs_idx(idx, val, name="val"):
     return idx.shape
 
 
+def _pairs_val(val):
+    """(B, k) of val [B, k], bf16 / fp32, contiguous"""
+    if val.dim() != 2 or val.shape[0] < 1 or val.shape[1] < 1 or val.dtype not in _DT or not val.is_contiguous():
+        raise ValueError(f"val must be a contiguous bf16 or fp32 [rows >= 1, k >= 1] tensor, got {val.dtype} "
+                         f"{tuple(val.shape)}")
+    return val.shape
+
+
 def _grouped(perm, seg, dev):
     """(P, h) of the pairs grouped by latent: perm [P] int32, seg [h + 1] int64, contiguous on dev"""
     if perm.dtype != torch.int32 or perm.dim() != 1 or not perm.is_contiguous() or perm.device != dev:
@@ -870,8 +895,7 @@ def pairs_by_latent(idx, h):
     every sort gives one order, and the counts are integers."""
     if idx.dim() != 2 or idx.dtype not in (torch.int32, torch.int64):
         raise ValueError(f"idx must be an int32 or int64 [rows, k] tensor, got {idx.dtype} {tuple(idx.shape)}")
-    if isinstance(h, bool) or not isinstance(h, int) or h < 1:
-        raise ValueError(f"h must be an int >= 1, got {h!r}")
+    _int_at_least(h, "h")
     Bk = idx.numel()
     if Bk > 2 ** 31 - 1:
         raise ValueError(f"rows * k must stay below 2^31, got {Bk}")
@@ -893,28 +917,19 @@ def pairs_grad_values(idx, W_dec, g, n, d, val=None, h=None, dot=None, total=Non
     A slot whose index is outside [0, h) gives +0 (h defaults to W_dec's rows).  idx [B, k] int32, contiguous; W_dec
     [>= h, >= n * d] and g may be column slices of wider matrices.  -> (dot or None, total or None)."""
     B, k = _pairs_idx(idx, val)
-    for name, v in (("n", n), ("d", d)):
-        if isinstance(v, bool) or not isinstance(v, int) or v < 1:
-            raise ValueError(f"{name} must be an int >= 1, got {v!r}")
-    if d % 8:
-        raise ValueError(f"d must be a multiple of 8, got {d}")
+    _int_at_least(n, "n")
+    _mult8(d, "d")
     K, dt, dev = n * d, g.dtype, idx.device
     if dt not in _DT:
         raise ValueError(f"g must be bf16 or fp32, got {dt}")
-    if g.dim() != 2 or g.shape[0] != B or g.shape[1] < K or g.device != dev:
-        raise ValueError(f"g must be [{B}, >= {K}] on {dev}, got {tuple(g.shape)}")
-    if W_dec.dim() != 2 or W_dec.shape[1] < K or W_dec.dtype != dt or W_dec.device != dev:
-        raise ValueError(f"W_dec must be [h, >= {K}] of {dt} on {dev}, got {W_dec.dtype} {tuple(W_dec.shape)}")
+    pg, ldg = _rows(g, B, K, dt, dev, "g")
+    pw, ldw, h = _decoder(W_dec, K, dt, dev, h)
     if val is not None and val.dtype != dt:
         raise ValueError(f"val must have g's dtype {dt}, got {val.dtype}")
-    h = W_dec.shape[0] if h is None else h
-    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
-        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
     _dense(dot, torch.float32, (B, k, n), dev, "dot")
     _dense(total, torch.float32, (B, k), dev, "total")
     if dot is None and total is None and not want_dot and not want_total:
         raise ValueError("at least one of dot and total is needed")
-    (pw, ldw), (pg, ldg) = _pitched(W_dec, K, "W_dec"), _pitched(g, K, "g")
     stream = _stream(idx)
     if total is None and want_total:
         total = torch.empty(B, k, dtype=torch.float32, device=dev)
@@ -935,29 +950,20 @@ def pairs_grad_decoder(perm, seg, val, g, K, out=None, ws=None):
     list longer than PAIRS_GRAD_SPLIT in pieces of that length, added in order), rounded once; a latent without pairs
     gets a row of +0.  val [B, k] contiguous, g [B, >= K] and out [h, >= K] of its dtype (column slices keep their
     pitch); ws: fp32, at least pairs_grad_decoder_ws_floats(len(perm), K) elements (allocated when None)."""
-    if val.dim() != 2 or val.shape[0] < 1 or val.shape[1] < 1 or val.dtype not in _DT or not val.is_contiguous():
-        raise ValueError(f"val must be a contiguous bf16 or fp32 [rows >= 1, k >= 1] tensor, got {val.dtype} "
-                         f"{tuple(val.shape)}")
-    B, k = val.shape
+    B, k = _pairs_val(val)
     dt, dev = val.dtype, val.device
     P, h = _grouped(perm, seg, dev)
-    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
-        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
-    if g.dim() != 2 or g.shape[0] != B or g.shape[1] < K or g.dtype != dt or g.device != dev:
-        raise ValueError(f"g must be [{B}, >= {K}] of {dt} on {dev}, got {g.dtype} {tuple(g.shape)}")
-    if out is not None and (out.dim() != 2 or out.shape[0] != h or out.shape[1] < K or out.dtype != dt
-                            or out.device != dev):
-        raise ValueError(f"out must be [{h}, >= {K}] of {dt} on {dev}, got {out.dtype} {tuple(out.shape)}")
+    _mult8(K, "K")
+    pg, ldg = _rows(g, B, K, dt, dev, "g")
+    po, ldo = _rows(out, h, K, dt, dev, "out", True)
     need = (P // PAIRS_GRAD_SPLIT) * K
-    if ws is not None and (ws.dtype != torch.float32 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
-        raise ValueError(f"ws must be a contiguous fp32 tensor of at least {need} elements on {dev}")
-    pg, ldg = _pitched(g, K, "g")
+    _scratch(ws, torch.float32, need, dev)
     stream = _stream(val)
     if out is None:
         out = torch.empty(h, K, dtype=dt, device=dev)
+        po, ldo = _ptr(out), K
     if ws is None and need:
         ws = torch.empty(pairs_grad_decoder_ws_floats(P, K), dtype=torch.float32, device=dev)
-    po, ldo = _pitched(out, K, "out")
     check(lib().cc_pairs_grad_decoder(_ptr(perm), P, _ptr(seg), h, _ptr(val), B, k, pg, ldg, K, dtype_code(dt), po, ldo,
                                       _ptr(ws), stream))
     return out
@@ -992,15 +998,13 @@ def pairs_group(idx, h, perm=None, seg=None, ws=None):
     inside [0, B k).  ws: uint8, at least pairs_group_ws_bytes(B, k, h) bytes, 16-byte aligned (allocated when None)."""
     B, k = _pairs_idx(idx, None)
     dev = idx.device
-    if isinstance(h, bool) or not isinstance(h, int) or h < 1:
-        raise ValueError(f"h must be an int >= 1, got {h!r}")
+    _int_at_least(h, "h")
     _dense(perm, torch.int32, (B * k,), dev, "perm")
     _dense(seg, torch.int64, (h + 1,), dev, "seg")
     need = pairs_group_ws_bytes(B, k, h)
     if need == 0:
         raise ValueError(f"pairs_group: (rows, k, h) = ({B}, {k}, {h}) is out of the kernel's range")
-    if ws is not None and (ws.dtype != torch.uint8 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
-        raise ValueError(f"ws must be a contiguous uint8 tensor of at least {need} elements on {dev}")
+    _scratch(ws, torch.uint8, need, dev)
     stream = _stream(idx)
     if perm is None:
         perm = torch.empty(B * k, dtype=torch.int32, device=dev)
@@ -1019,21 +1023,13 @@ def decode_pairs_partial(val, idx, W_dec, K, h=None, recon=None):
     int32, contiguous; W_dec [>= h, >= K] of val's dtype (column slices keep their pitch)."""
     B, k = _pairs_idx(idx, val)
     dt, dev = val.dtype, val.device
-    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
-        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
-    if W_dec.dim() != 2 or W_dec.shape[1] < K or W_dec.dtype != dt or W_dec.device != dev:
-        raise ValueError(f"W_dec must be [h, >= {K}] of {dt} on {dev}, got {W_dec.dtype} {tuple(W_dec.shape)}")
-    h = W_dec.shape[0] if h is None else h
-    if isinstance(h, bool) or not isinstance(h, int) or not 1 <= h <= W_dec.shape[0]:
-        raise ValueError(f"h must be an int in 1..{W_dec.shape[0]} (W_dec's rows), got {h!r}")
-    if recon is not None and (recon.dim() != 2 or recon.shape[0] != B or recon.shape[1] < K
-                              or recon.dtype != torch.float32 or recon.device != dev):
-        raise ValueError(f"recon must be fp32 [{B}, >= {K}] on {dev}, got {recon.dtype} {tuple(recon.shape)}")
-    pw, ldw = _pitched(W_dec, K, "W_dec")
+    _mult8(K, "K")
+    pw, ldw, h = _decoder(W_dec, K, dt, dev, h)
+    pr, ldr = _rows(recon, B, K, torch.float32, dev, "recon", True)
     stream = _stream(val)
     if recon is None:
         recon = torch.empty(B, K, dtype=torch.float32, device=dev)
-    pr, ldr = _pitched(recon, K, "recon")
+        pr, ldr = _ptr(recon), K
     check(lib().cc_decode_pairs_partial(_ptr(val), _ptr(idx), B, k, pw, ldw, h, K, dtype_code(dt), pr, ldr, stream))
     return recon
 
@@ -1053,18 +1049,13 @@ def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq
     stored values, pairs_wgrad_parts(h) fp32 partials per parameter.  val [B, k] (bf16 / fp32) and g_pre fp32 [B, k],
     contiguous; g_recon, x [B, >= K] and dW_dec, dW_enc [h, >= K] of val's dtype (pitches kept); db_enc [h] of it; ws:
     fp32, at least pairs_wgrad_ws_floats(len(perm), K) elements (allocated when None)."""
-    if val.dim() != 2 or val.shape[0] < 1 or val.shape[1] < 1 or val.dtype not in _DT or not val.is_contiguous():
-        raise ValueError(f"val must be a contiguous bf16 or fp32 [rows >= 1, k >= 1] tensor, got {val.dtype} "
-                         f"{tuple(val.shape)}")
-    B, k = val.shape
+    B, k = _pairs_val(val)
     dt, dev = val.dtype, val.device
     P, h = _grouped(perm, seg, dev)
     _dense(g_pre, torch.float32, (B, k), dev, "g_pre")
-    if isinstance(K, bool) or not isinstance(K, int) or K < 8 or K % 8:
-        raise ValueError(f"K must be an int multiple of 8, got {K!r}")
-    for name, t, rows in (("g_recon", g_recon, B), ("x", x, B), ("dW_dec", dW_dec, h), ("dW_enc", dW_enc, h)):
-        if t is None or t.dim() != 2 or t.shape[0] != rows or t.shape[1] < K or t.dtype != dt or t.device != dev:
-            raise ValueError(f"{name} must be [{rows}, >= {K}] of {dt} on {dev}")
+    _mult8(K, "K")
+    (pg, ldg), (px, ldx) = _rows(g_recon, B, K, dt, dev, "g_recon"), _rows(x, B, K, dt, dev, "x")
+    (pd, ldd), (pe, lde) = _rows(dW_dec, h, K, dt, dev, "dW_dec"), _rows(dW_enc, h, K, dt, dev, "dW_enc")
     _dense(db_enc, dt, (h,), dev, "db_enc")
     parts = pairs_wgrad_parts(h)
     for name, t in (("sq_dec", sq_dec), ("sq_enc", sq_enc), ("sq_b_enc", sq_b_enc)):
@@ -1072,10 +1063,7 @@ def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq
     if g_pre is None or db_enc is None or sq_dec is None or sq_enc is None or sq_b_enc is None:
         raise ValueError("g_pre, db_enc and the three sq partials are all needed")
     need = (P // PAIRS_GRAD_SPLIT) * (2 * K + 8)
-    if ws is not None and (ws.dtype != torch.float32 or ws.device != dev or not ws.is_contiguous() or ws.numel() < need):
-        raise ValueError(f"ws must be a contiguous fp32 tensor of at least {need} elements on {dev}")
-    (pg, ldg), (px, ldx) = _pitched(g_recon, K, "g_recon"), _pitched(x, K, "x")
-    (pd, ldd), (pe, lde) = _pitched(dW_dec, K, "dW_dec"), _pitched(dW_enc, K, "dW_enc")
+    _scratch(ws, torch.float32, need, dev)
     stream = _stream(val)
     if ws is None and need:
         ws = torch.empty(pairs_wgrad_ws_floats(P, K), dtype=torch.float32, device=dev)
@@ -1120,8 +1108,7 @@ def batch_topk(acts, h, n_keep, weight=None, out=None, colsum_part=None, l0_part
     of one element on the device) with beta in [0, 1): the running threshold the last selection launch folds T into
     (T itself while it is < 0).  Returns out."""
     B, ld = _batch_topk_args(acts, h, weight, out, colsum_part, l0_part, row_count)
-    if isinstance(n_keep, bool) or not isinstance(n_keep, int) or n_keep < 1:
-        raise ValueError(f"n_keep must be an int >= 1, got {n_keep!r}")
+    _int_at_least(n_keep, "n_keep")
     if out is None and info is None and row_count is None:
         raise ValueError("at least one of out, info and row_count is needed")
     dev = acts.device

@@ -15,6 +15,7 @@ import torch
 import crosscoder_amd as ca
 from crosscoder_amd import ops
 from oracle import cpu_reference as O
+from tests import _decode_pairs_ref as dref
 from tests import _pairs_grad_ref as pref
 from tests import _sparse_step_ref as ref
 from tests._golden import load
@@ -28,6 +29,13 @@ BITS = {torch.bfloat16: torch.int16, torch.float32: torch.int32, torch.int32: to
 # (B, n, d, h, k): base; nothing a tile multiple; n = 4; skewed
 SHAPES = [(64, 2, 32, 256, 8), (96, 2, 40, 200, 5), (128, 4, 64, 256, 16), (300, 2, 32, 128, 8)]
 SKEW = SHAPES[3]
+# cc_pairs_wgrad only: 257 eight-column groups (a second, ragged pass of the lane loop) on SKEW's list of latent 3
+WIDE_SKEW = (300, 1, 2056, 64, 8)
+SKEWED = (SKEW, WIDE_SKEW)
+# the decode only, cc_decode_pairs' cases (tests/_decode_pairs_ref.make_case): K = 2088, one chunk of 2048 columns and a
+# ragged 40; k beyond one staged tile, staged again for each of two chunks; one small
+DECODE_WIDE = [(5, 3, 696, 64, 9), (3, 2, 1032, 512, 300)]
+DECODE_SMALL = (3, 2, 40, 200, 5)
 CAN = 1234.0
 ICAN = -77
 
@@ -44,12 +52,19 @@ def bits(t):
 def case(shape, dt):
     """The shared case of a shape: CPU operands and references (computed once, never written)."""
     B, n, d, h, k = shape
-    c = ref.make_case(B, n, d, h, k, DT[dt], skew=shape == SKEW)
-    if shape == SKEW:
+    c = ref.make_case(B, n, d, h, k, DT[dt], skew=shape in SKEWED)
+    if shape in SKEWED:
         ref.assert_skewed(c["idx"], h, k)
     c["perm"], c["seg"] = pref.by_latent_loop(c["idx"], h)
     c["len"] = torch.tensor(c["seg"][1:]) - torch.tensor(c["seg"][:-1])
     return c
+
+
+@functools.lru_cache(maxsize=None)
+def decode_case(shape, dt):
+    """The shared decode-only case of a shape: cc_decode_pairs' operands under this file's names"""
+    c = dref.make_case(*shape, DT[dt])
+    return {"val": c["val"], "idx": c["idx"], "W_dec": c["W"]}
 
 
 def on_gpu(c, *names):
@@ -102,11 +117,11 @@ def test_group_equals_pairs_by_latent(name, idx, h):
 
 # ---------------------------------------------------------------- cc_decode_pairs_partial
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
-@pytest.mark.parametrize("shape", SHAPES, ids=sid)
+@pytest.mark.parametrize("shape", SHAPES + DECODE_WIDE, ids=sid)
 def test_decode_partial_is_the_fma_chain(shape, dt):
     B, n, d, h, k = shape
     K = n * d
-    c = case(shape, dt)
+    c = decode_case(shape, dt) if shape in DECODE_WIDE else case(shape, dt)
     val, idx, W = on_gpu(c, "val", "idx", "W_dec")
     want = ref.decode_partial_f32(c["val"], c["idx"], c["W_dec"], h, K)
     got = ops.decode_pairs_partial(val, idx, W, K)
@@ -133,6 +148,19 @@ def test_decode_partial_is_the_fma_chain(shape, dt):
     assert torch.equal(bits(ops.decode_pairs_partial(val, idx, W, K)), bits(got))           # two calls
 
 
+@pytest.mark.parametrize("dt", ["bf16", "fp32"])
+@pytest.mark.parametrize("shape", DECODE_WIDE + [DECODE_SMALL], ids=sid)
+def test_decode_pairs_is_the_rounded_partial(shape, dt):
+    """cc_decode_pairs with a zero b_dec is cc_decode_pairs_partial rounded once: the same chain from +0"""
+    B, n, d, h, k = shape
+    K = n * d
+    val, idx, W = on_gpu(decode_case(shape, dt), "val", "idx", "W_dec")
+    recon, _ = ops.decode_pairs(val, idx, W, torch.zeros(K, dtype=DT[dt], device="cuda"), n, d)
+    partial = ops.decode_pairs_partial(val, idx, W, K)
+    assert float(partial.abs().sum()) > 0
+    assert torch.equal(bits(recon), bits(partial.to(DT[dt])))
+
+
 # ---------------------------------------------------------------- cc_pairs_wgrad
 def run_wgrad(c, shape, dt, h_kernel=None, canaries=False):
     B, n, d, h, k = shape
@@ -155,7 +183,7 @@ def run_wgrad(c, shape, dt, h_kernel=None, canaries=False):
 
 
 @pytest.mark.parametrize("dt", ["bf16", "fp32"])
-@pytest.mark.parametrize("shape", SHAPES, ids=sid)
+@pytest.mark.parametrize("shape", SHAPES + [WIDE_SKEW], ids=sid)
 def test_wgrad_against_the_row_kernel_and_the_restatements(shape, dt):
     B, n, d, h, k = shape
     K = n * d
@@ -185,16 +213,17 @@ def test_wgrad_against_the_row_kernel_and_the_restatements(shape, dt):
         assert bool((err <= tol).all())
     # empty lists: rows of +0
     empty = c["len"] == 0
-    assert shape != SKEW or int(empty.sum()) >= 24
+    assert shape not in SKEWED or int(empty.sum()) >= 24
     if empty.any():
         assert bool((bits(got_d.cpu())[empty] == 0).all()) and bool((bits(got_e.cpu())[empty] == 0).all())
         assert bool((bits(got_b.cpu())[empty] == 0).all())
-    if shape == SKEW:
+    if shape in SKEWED:
         assert int(c["len"][3]) == B and B > 2 * ref.SPLIT and B % ref.SPLIT        # two full pieces and a rest
-    # squared sums of the stored values.  D = 18 here: 8 additions for the one 8-column group a lane stores (K / 8 <= 256
-    # groups, one row per workgroup), 6 for the butterfly, 4 for the waves (tests/_sparse_step_ref.py)
+    # squared sums of the stored values.  D = 18: 8 additions for the one 8-column group a lane stores (K / 8 <= 256
+    # groups, one row per workgroup), 6 for the butterfly, 4 for the waves (tests/_sparse_step_ref.py); WIDE_SKEW's lane
+    # 0 stores a second group: 26
     D = ref.sq_chain_depth(h, K)
-    assert D == 18 and parts == h
+    assert D == (26 if shape == WIDE_SKEW else 18) and parts == h
     for name, part, stored in (("dW_dec", r["sq"][0], got_d), ("dW_enc", r["sq"][1], got_e), ("db_enc", r["sq"][2], got_b)):
         total = float(part[:parts].double().sum())
         exact = float(stored.double().pow(2).sum())
@@ -208,7 +237,7 @@ def test_wgrad_against_the_row_kernel_and_the_restatements(shape, dt):
     assert bool((r["db"][h:] == CAN).all())
     need = ops.pairs_wgrad_ws_floats(B * k, K)
     assert bool((r["ws"][need:] == CAN).all())
-    assert shape != SKEW or need == (B * k // ref.SPLIT) * (2 * K + 8)
+    assert shape not in SKEWED or need == (B * k // ref.SPLIT) * (2 * K + 8)
     # two calls: equal bits
     r2 = run_wgrad(c, shape, dt, canaries=True)
     for key in ("dWd", "dWe", "db"):
