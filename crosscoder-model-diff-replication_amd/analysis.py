@@ -41,8 +41,8 @@ def fold_activation_scaling_factor(cross_coder, *scaling_factors, fold_decoder=T
     # the encoder-only variant passes no decoder pointers
     ops.fold_scaling(a.W_enc_hk, a.W_dec_hk if fold_decoder else None, a.b_dec_flat if fold_decoder else None, s,
                      a.n, a.d)
-    a.updates += 1  # (a kernel wrote the params: what is cached from them is stale, engine.Arena.updates)
-    return cross_coder
+    # a kernel wrote the params: what any step workspace, the selection weights and the masters carry from them is stale
+    return cross_coder.params_written()
 
 
 def sae_vis_export(cross_coder, *scaling_factors, dtype=torch.bfloat16):

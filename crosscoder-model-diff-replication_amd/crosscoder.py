@@ -284,6 +284,21 @@ class CrossCoder(nn.Module):
             self._ws = None
         return self._arena
 
+    def params_written(self):
+        """Tell the crosscoder that its parameters were written in a way torch's version counters do not show: by a
+        kernel (fold_activation_scaling_factor and LatentResampler call this themselves), or in place through
+        `param.data` / a raw pointer.  Orders torch's current stream after pending Adam work on the side stream
+        (launching its deferred rows), and counts the write in Arena.updates, which everything carried from the
+        parameters is keyed on: the decoder norms, norm partials and W_dec^T of every step workspace on the arena (the
+        crosscoder's, a Trainer's sparse one, a ShardedTrainer's), BatchTopK's selection weights and, in master mode,
+        the fp32 masters, which are re-seeded where they no longer round to their parameter.  The next forward
+        re-derives all of it.  Call it after the write and before the next step, get_losses or encode; a writer on
+        another stream orders itself after `arena().wait_pending()` first.  Returns the crosscoder."""
+        a = self.arena()
+        a.wait_pending()
+        a.updates += 1
+        return self
+
     def theta(self):
         """fp32 [kernel h] on the arena's device: the JumpReLU thresholds as the kernels read them, of which the
         parameter jump_threshold is the first dict_size; re-packed if something (e.g. .to()) replaced the parameter."""
@@ -379,10 +394,10 @@ class CrossCoder(nn.Module):
 
     def _selection_weights(self):
         """fp32 [kernel h]: the summed per-model decoder norms (0 for the padding latents), from cc_dec_norms; kept
-        while W_dec is the same storage, unwritten by torch (version counter) and by Adam (Arena.updates)."""
+        while W_dec is the same storage, unwritten by torch (version counter) and by kernels (Arena.updates)."""
         a = self.arena()
         a.wait_pending()
-        key = (*engine._norms_token(a), a.updates)
+        key = engine._norms_token(a)
         if self._sel_w is None or self._sel_w[0] != key:
             self._sel_w = (key, ops.dec_norms(a.W_dec_hk, self._hp, self.n_models, self._dp)[1])
         return self._sel_w[1]
@@ -546,6 +561,9 @@ class CrossCoder(nn.Module):
         return super().state_dict(*args, **kwargs)
 
     def load_state_dict(self, state_dict, *args, **kwargs):
+        # torch copies into self._parameters directly (no attribute access): the decoder half may still be updating on
+        # the trainer's side stream, and its deferred rows would otherwise be applied after the load
+        self._sync_pending()
         # a BatchTopK crosscoder takes the reference's four tensors as they are (e.g. a ReLU checkpoint to train on):
         # its threshold then stays what it is
         if self.activation == "batch_topk" and "threshold" not in state_dict:

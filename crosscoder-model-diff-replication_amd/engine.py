@@ -37,6 +37,7 @@ prep, G1, the loss kernels and adam, and runs G2 and the whole backward on the s
 row (csrc/sparse_step.hip, csrc/pairs_grad.hip) instead of G2, G3 and G4G5.
 """
 import contextlib
+import itertools
 
 import torch
 
@@ -110,6 +111,8 @@ class Arena:
     h, d are the kernel dims (padded_dims); ref = (dict_size, d_in) of the reference-shaped views
     when they differ."""
 
+    _serials = itertools.count()
+
     def __init__(self, h, n, d, dtype, device, data=None, ref=None):
         self.h, self.n, self.d = h, n, d
         self.h_ref, self.d_ref = ref if ref is not None else (h, d)
@@ -132,9 +135,11 @@ class Arena:
         self.pending_rest = None
         # a stream already ordered after `pending` by a launch that waited for the Adam in its kernel
         self.pending_ordered = None
-        # Adam launches on this arena so far: they write it without bumping torch's version counters, so what is
-        # cached from the params outside the step (CrossCoder's selection weights) is keyed on this as well
+        # kernel writes of this arena so far (Adam launches, the scaling-factor fold, the resampler: whoever calls
+        # CrossCoder.params_written): they bump no torch version counter, so everything cached from the params is
+        # keyed on this as well (_norms_token, FusedAdam._arena_token, CrossCoder's selection weights)
         self.updates = 0
+        self.serial = next(Arena._serials)  # (a re-packed arena may get a freed arena's address back)
 
     def enc_part(self):
         return self.data[:self.split]
@@ -388,10 +393,11 @@ def transposed_wgrad(B, K, h, dtype):
 
 
 def _norms_token(P):
-    # the decoder norms stay valid while W_dec is the same storage and has not been written in
-    # place through torch (every such write bumps the view's version counter; our own Adam kernel
-    # does not, and norms_for_next() is launched right after it)
-    return (P.W_dec_hk.data_ptr(), P.W_dec_hk._version)
+    # what the workspace carries from W_dec (norms, norm partials, W_dec^T) stays valid while W_dec is the same storage
+    # of the same arena, has not been written in place through torch (every such write bumps the version counter all
+    # views of the arena share) and no kernel has written the arena since (Arena.updates: the step's Adam, which
+    # derives the carry right after, and every other kernel writer -- CrossCoder.params_written)
+    return (P.serial, P.W_dec_hk.data_ptr(), P.W_dec_hk._version, P.updates)
 
 
 def norms_for_next(ws, P):
@@ -400,6 +406,7 @@ def norms_for_next(ws, P):
     (clip_and_adam(side_stream=...) launches them on the side stream itself.)"""
     if ws.norms_token == _norms_token(P):
         return
+    ws.norms_fin_pending = False  # (as decoder_norms: nothing finalises over what is derived here)
     _decoder_derived(ws, P)
     ws.norms_token = _norms_token(P)
 
@@ -422,23 +429,16 @@ def flush_norms(ws):
             ops.dec_norms_finalize(ws.norm_part, ws.h, ws.n, ws.d, ws.norms, ws.tn, ws.inv_norms)
 
 
-def invalidate_decoder_derived(ws):
-    """After a kernel other than the step's Adam wrote W_dec (resample.py): drop what the workspace carries from the
-    last Adam launch to the next forward, which then re-derives it from W_dec (decoder_norms).  The token alone does
-    not do: it is keyed on torch's version counter, which a kernel write does not bump, and norm partials pending
-    their finaliser (norms_fin_pending, set by the first reader's wait for the side-stream Adam) would be finalised
-    over the re-derived norms by the next G2 launch.  Call it after Arena.wait_pending()."""
-    if ws is not None:
-        ws.norms_token = None
-        ws.norms_fin_pending = False
-
-
 def decoder_norms(ws, P):
-    """||W_dec[h, m]||, their sum over m and inverses (crosscoder.py:123-125), unless still fresh."""
-    if getattr(ws, "norms_token", None) == _norms_token(P):
-        ws.norms_token = None  # consumed: W_dec changes with this step's Adam
+    """||W_dec[h, m]||, their sum over m and inverses (crosscoder.py:123-125), unless still fresh.  Call it after
+    Arena.wait_pending(): the first reader's wait for the side-stream Adam sets norms_fin_pending, and norm partials
+    pending their finaliser are Adam's, of the W_dec it wrote -- where W_dec was written since (the token moved), they
+    are dropped with the token, or the next G2 launch / flush_norms would finalise them over the re-derived norms."""
+    fresh = getattr(ws, "norms_token", None) == _norms_token(P)
+    ws.norms_token = None  # consumed: W_dec changes with this step's Adam
+    if fresh:
         return
-    ws.norms_token = None
+    ws.norms_fin_pending = False
     _decoder_derived(ws, P)
 
 

@@ -167,13 +167,12 @@ class LatentResampler:
         done = ops.resample_write(self._x[:self.filled], rows, latents, cc._hp, enc_norm, dec_norm, a.data,
                                   master=None if master is None else master.data, exp_avg=m, exp_avg_sq=v)
         # The kernel wrote the arenas without bumping a version counter: what is derived from the parameters is
-        # re-keyed (the selection weights follow Arena.updates; the masters are already the unrounded rows, so their
-        # token moves along and they are not rebuilt from the rounded parameters) or dropped (the step workspace's
-        # carried decoder norms, norm partials and W_dec^T)
-        a.updates += 1
+        # re-keyed with Arena.updates (params_written): the selection weights and every step workspace's carried decoder
+        # norms, norm partials and W_dec^T are derived again by their next reader; the masters are already the
+        # unrounded rows, so their token moves along and they are not rebuilt from the rounded parameters
+        cc.params_written()
         if master is not None:
             optimizer.master_updated()
-        engine.invalidate_decoder_derived(cc._ws)
         out["written"] = done.bool()
         out["enc_norm"], out["dec_norm"] = enc_norm, dec_norm
         out["resampled"] = int(done.sum())

@@ -518,9 +518,9 @@ class Trainer:
     def resample_dead_latents(self, resampler, dead=None, u=None):
         """Re-seed dead latents between two steps (LatentResampler.apply with this trainer's optimizer): orders
         torch's current stream after the last step's launches on both of its streams, applies `resampler` (built on
-        this trainer's crosscoder and filled by the caller; dead, u: apply's), drops what the last step's workspace
-        carries of the old decoder, and -- AuxK trainers -- zeroes tokens_since_fired of the re-seeded latents and
-        refreshes the dead count.  Returns apply's dict."""
+        this trainer's crosscoder and filled by the caller; dead, u: apply's; its CrossCoder.params_written() drops what
+        the last step's workspace carries of the old decoder), and -- AuxK trainers -- zeroes tokens_since_fired of the
+        re-seeded latents and refreshes the dead count.  Returns apply's dict."""
         if resampler.cc is not self.crosscoder:
             raise ValueError("resampler must be built on this trainer's crosscoder")
         self.synchronize()
@@ -528,8 +528,8 @@ class Trainer:
         if self._side is not None:
             torch.cuda.current_stream(dev).wait_stream(self._side)
         out = resampler.apply(self.optimizer, dead=dead, u=u)
+        # (what the last step's workspace carries of the old decoder is keyed on Arena.updates, which apply counted up)
         if out["resampled"]:
-            engine.invalidate_decoder_derived(self._last_ws)
             if self.auxk is not None:
                 tsf = self._since_fired()
                 tsf[out["latents"][out["written"]]] = 0
