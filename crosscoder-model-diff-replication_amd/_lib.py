@@ -167,6 +167,10 @@ SIGNATURES = {
     "cc_pairs_wgrad_parts": (_i64, [_i64]),
     "cc_pairs_wgrad": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i64, _p, _p,
                             _p, _p, _p, _p]),
+    "cc_dead_compact": (_i, [_p, _i64, _i64, _i64, _p, _i64, _p, _p, _p]),
+    "cc_compact_gather": (_i, [_p, _i64, _i64, _p, _i64, _i64, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
+    "cc_pairs_wgrad_add": (_i, [_p, _i64, _p, _i64, _p, _p, _i64, _i, _p, _i64, _p, _i64, _i64, _i, _p, _i64, _p, _i64, _p,
+                                _p, _p, _p, _p, _p, _i64, _p, _i64, _p, _i64, _p, _p]),
 }
 
 _lib = None

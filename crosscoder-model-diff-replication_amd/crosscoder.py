@@ -178,6 +178,23 @@ def sparse_step_of(cfg):
     return sp
 
 
+def auxk_compact_of(cfg):
+    """cfg["auxk_compact"] (framework extension; the key travels in the checkpoint's cfg json): a bool, absent or False:
+    off.  True needs cfg["auxk_coeff"] > 0 and cfg["sparse_step"]: Trainer.step then serves the AuxK loss under the
+    sparse step, running the aux GEMMs over the compacted dead set instead of the whole dictionary (DESIGN.md section
+    3.22).  The dense TopK / BatchTopK step's AuxK is unchanged and does not take the key."""
+    ac = cfg.get("auxk_compact", False)
+    if not isinstance(ac, bool):
+        raise ValueError(f"cfg['auxk_compact'] must be a bool, got {ac!r}")
+    coeff = cfg.get("auxk_coeff", 0)
+    if ac and not (isinstance(coeff, (int, float)) and not isinstance(coeff, bool) and coeff > 0):
+        raise ValueError("cfg['auxk_compact'] needs cfg['auxk_coeff'] > 0: there is no aux loss to compact")
+    if ac and not cfg.get("sparse_step", False):
+        raise ValueError("cfg['auxk_compact'] needs cfg['sparse_step']: the compacted aux path is built for the sparse "
+                         "step only")
+    return ac
+
+
 class CrossCoder(nn.Module):
     def __init__(self, cfg, n_models: Optional[int] = None, init_W_dec: Optional[torch.Tensor] = None):
         """init_W_dec (framework extension): start from this decoder ([h, n, d], W_enc = its rearranged
@@ -192,6 +209,7 @@ class CrossCoder(nn.Module):
         self.auxk = auxk_options(cfg, self.n_models)  # (auxk_coeff, k_aux, dead_tokens) or None: Trainer.step's
         master_weights_of(cfg)  # (validated here; Trainer's optimizer is what it switches)
         sparse_step_of(cfg)  # (validated here; Trainer.step is what it switches)
+        auxk_compact_of(cfg)  # (likewise; after auxk_options and sparse_step_of, whose own errors come first)
         self.dtype = DTYPES[cfg["enc_dtype"]]
         if self.dtype not in (torch.float32, torch.bfloat16):
             raise TypeError("crosscoder_amd kernels support enc_dtype 'bf16' and 'fp32'")

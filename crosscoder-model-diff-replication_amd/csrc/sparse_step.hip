@@ -26,6 +26,9 @@
 //   fp32 totals, rounded once).  Squared sums of the STORED values: a lane folds its elements in the order it stores
 //   them (fma(r, r, sq)), the 64 lanes meet in the xor butterfly, thread 0 adds the four waves in order: one partial
 //   per workgroup of launch 2 and parameter, at sq_*[blockIdx.x].
+//
+// cc_pairs_wgrad_add: cc_pairs_wgrad whose launch 2 also takes, for a latent with a compact slot (the dead set of the
+//   AuxK loss, auxk_compact.hip), a row of three addends into the fp32 sums before the one rounding (pw_row_body<ADD>).
 #include "pairs_common.h"
 
 namespace cc {
@@ -196,12 +199,23 @@ __global__ __launch_bounds__(PAIRS_THREADS) void pw_piece_kernel(PairList a, int
 
 // launch 2: every row of dW_dec, dW_enc and db_enc, and the workgroup's squared-sum partials (one workspace row in
 // flight: with PAIRS_UNROLL of them the kernel leaves the 4-waves-per-SIMD register bracket)
-template <int DT>
-__global__ __launch_bounds__(PAIRS_THREADS) void pw_row_kernel(PairList a, int64_t P, const int64_t* __restrict__ seg,
-                                                               int64_t h, uint32_t ng, const float* __restrict__ ws,
-                                                               void* __restrict__ dWd, int64_t ldd, void* __restrict__ dWe,
-                                                               int64_t lde, void* __restrict__ db, float* __restrict__ sq_dec,
-                                                               float* __restrict__ sq_enc, float* __restrict__ sq_b) {
+// ADD (cc_pairs_wgrad_add): a latent j with a compact slot s = slot[j] in [0, d_pad) takes row s of the addends in --
+// float(aWd[s]), float(aWe[s]), float(ab[s]) added to the lane's fp32 sums after the list's and before the one
+// rounding; the squared sums stay those of the stored values
+struct PairAddend {
+  const int32_t* slot;  // [h]
+  const void* aWd;      // [d_pad][lda_d]
+  const void* aWe;      // [d_pad][lda_e]
+  const void* ab;       // [d_pad]
+  int64_t lda_d, lda_e;
+  uint32_t d_pad;
+};
+
+template <int DT, bool ADD>
+CC_DEV void pw_row_body(const PairList& a, int64_t P, const int64_t* __restrict__ seg, int64_t h, uint32_t ng,
+                        const float* __restrict__ ws, void* __restrict__ dWd, int64_t ldd, void* __restrict__ dWe,
+                        int64_t lde, void* __restrict__ db, float* __restrict__ sq_dec, float* __restrict__ sq_enc,
+                        float* __restrict__ sq_b, const PairAddend& ad) {
   typedef typename Elem<DT>::T T;
   __shared__ float wred[3][PAIRS_NW];
   float sqd = 0.f, sqe = 0.f, sqb = 0.f;
@@ -211,6 +225,17 @@ __global__ __launch_bounds__(PAIRS_THREADS) void pw_row_kernel(PairList a, int64
       const int64_t col = (int64_t)G * 8;
       ListAcc acc;
       list_sum<DT, true, 1>(a, b, e, ws, (int64_t)ng * 8, col, acc);
+      if constexpr (ADD) {
+        const uint32_t s = (uint32_t)__builtin_amdgcn_readfirstlane(ad.slot[j]);
+        if (s < ad.d_pad) {  // (uniform; -1 and anything outside the addends add nothing)
+          float t[8];
+          load8<DT>(ad.aWd, (int64_t)s * ad.lda_d + col, t);
+          add8(acc.d, t);
+          load8<DT>(ad.aWe, (int64_t)s * ad.lda_e + col, t);
+          add8(acc.e, t);
+          if (G == 0) acc.b += Elem<DT>::to_f(((const T*)ad.ab)[s]);
+        }
+      }
       store8<DT>(dWd, j * ldd + col, acc.d);
       store8<DT>(dWe, j * lde + col, acc.e);
 #pragma unroll
@@ -252,6 +277,26 @@ __global__ __launch_bounds__(PAIRS_THREADS) void pw_row_kernel(PairList a, int64
     sq_enc[blockIdx.x] = t[1];
     sq_b[blockIdx.x] = t[2];
   }
+}
+
+template <int DT>
+__global__ __launch_bounds__(PAIRS_THREADS) void pw_row_kernel(PairList a, int64_t P, const int64_t* __restrict__ seg,
+                                                               int64_t h, uint32_t ng, const float* __restrict__ ws,
+                                                               void* __restrict__ dWd, int64_t ldd, void* __restrict__ dWe,
+                                                               int64_t lde, void* __restrict__ db, float* __restrict__ sq_dec,
+                                                               float* __restrict__ sq_enc, float* __restrict__ sq_b) {
+  pw_row_body<DT, false>(a, P, seg, h, ng, ws, dWd, ldd, dWe, lde, db, sq_dec, sq_enc, sq_b, PairAddend{});
+}
+
+template <int DT>
+__global__ __launch_bounds__(PAIRS_THREADS) void pw_row_add_kernel(PairList a, int64_t P, const int64_t* __restrict__ seg,
+                                                                   int64_t h, uint32_t ng, const float* __restrict__ ws,
+                                                                   void* __restrict__ dWd, int64_t ldd,
+                                                                   void* __restrict__ dWe, int64_t lde,
+                                                                   void* __restrict__ db, float* __restrict__ sq_dec,
+                                                                   float* __restrict__ sq_enc, float* __restrict__ sq_b,
+                                                                   PairAddend ad) {
+  pw_row_body<DT, true>(a, P, seg, h, ng, ws, dWd, ldd, dWe, lde, db, sq_dec, sq_enc, sq_b, ad);
 }
 
 static int64_t pw_groups(int64_t h) { return h < PAIRS_LIST_GROUPS ? h : PAIRS_LIST_GROUPS; }
@@ -315,17 +360,27 @@ int64_t cc_pairs_wgrad_ws_floats(int64_t P, int64_t K) {
 
 int64_t cc_pairs_wgrad_parts(int64_t h) { return h < 1 ? 0 : pw_groups(h); }
 
-int cc_pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val, const float* g_pre,
-                   int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx, int64_t K, int dtype,
-                   void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc, float* sq_dec,
-                   float* sq_enc, float* sq_b_enc, float* ws, void* stream) {
+// cc_pairs_wgrad and cc_pairs_wgrad_add (ad: its addends, all given or all null; d_pad: their rows)
+static int pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val, const float* g_pre,
+                       int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx, int64_t K, int dtype,
+                       void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc, float* sq_dec,
+                       float* sq_enc, float* sq_b_enc, float* ws, const PairAddend* ad, void* stream) {
   const int64_t nrows = P / PAIRS_SPLIT;
+  const bool add = ad && (ad->slot || ad->aWd || ad->aWe || ad->ab);
   const bool ptrs_ok = seg && val && g_pre && g_recon && x && dW_dec && dW_enc && db_enc && sq_dec && sq_enc &&
-                       sq_b_enc && (perm || P <= 0) && (ws || nrows <= 0);
-  const int rc = pairs_check(B, k, h, 1, K, {ldg, ldx, ld_dec, ld_enc}, true, P, true, ptrs_ok, &dtype, true,
-                             {g_recon, x, dW_dec, dW_enc, ws}, {perm, g_pre, sq_dec, sq_enc, sq_b_enc}, {seg},
-                             {val, db_enc});
+                       sq_b_enc && (perm || P <= 0) && (ws || nrows <= 0) &&
+                       (!add || (ad->slot && ad->aWd && ad->aWe && ad->ab));
+  const bool add_shape = !add || (ad->d_pad >= 1 && ad->lda_d >= K && ad->lda_e >= K);
+  int rc = pairs_check(B, k, h, 1, K, {ldg, ldx, ld_dec, ld_enc}, true, P, add_shape, ptrs_ok, &dtype,
+                       !add || ad->d_pad <= (uint32_t)INT32_MAX, {g_recon, x, dW_dec, dW_enc, ws},
+                       {perm, g_pre, sq_dec, sq_enc, sq_b_enc}, {seg}, {val, db_enc});
   if (rc != CC_OK) return rc;
+  if (add) {  // the addends' own alignment: the two matrices and their pitches 16 bytes, slot 4, ab its element
+    const int64_t es = dtype == CC_BF16 ? 2 : 4;
+    if (!aligned({ad->aWd, ad->aWe}, 15) || (((ad->lda_d | ad->lda_e) * es) & 15) || !aligned({ad->slot}, 3) ||
+        !aligned({ad->ab}, (uintptr_t)es - 1))
+      return CC_ERR_ALIGN;
+  }
   const PairList a{perm, val, g_pre, (uint32_t)(B * k), (uint32_t)k, g_recon, x, ldg, ldx};
   const uint32_t ng = (uint32_t)(K / 8);
   const hipStream_t st = (hipStream_t)stream;
@@ -334,10 +389,33 @@ int cc_pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h
     hipLaunchKernelGGL(CC_BY_DTYPE(pw_piece_kernel, dtype), grid, dim3(PAIRS_THREADS), 0, st, a, P, seg, h, ng, ws, nrows);
     CC_LAUNCH_CHECK();
   }
-  hipLaunchKernelGGL(CC_BY_DTYPE(pw_row_kernel, dtype), dim3((unsigned)pw_groups(h)), dim3(PAIRS_THREADS), 0, st, a, P,
-                     seg, h, ng, ws, dW_dec, ld_dec, dW_enc, ld_enc, db_enc, sq_dec, sq_enc, sq_b_enc);
+  if (add)
+    hipLaunchKernelGGL(CC_BY_DTYPE(pw_row_add_kernel, dtype), dim3((unsigned)pw_groups(h)), dim3(PAIRS_THREADS), 0, st, a,
+                       P, seg, h, ng, ws, dW_dec, ld_dec, dW_enc, ld_enc, db_enc, sq_dec, sq_enc, sq_b_enc, *ad);
+  else
+    hipLaunchKernelGGL(CC_BY_DTYPE(pw_row_kernel, dtype), dim3((unsigned)pw_groups(h)), dim3(PAIRS_THREADS), 0, st, a, P,
+                       seg, h, ng, ws, dW_dec, ld_dec, dW_enc, ld_enc, db_enc, sq_dec, sq_enc, sq_b_enc);
   CC_LAUNCH_CHECK();
   return CC_OK;
+}
+
+int cc_pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val, const float* g_pre,
+                   int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx, int64_t K, int dtype,
+                   void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc, float* sq_dec,
+                   float* sq_enc, float* sq_b_enc, float* ws, void* stream) {
+  return pairs_wgrad(perm, P, seg, h, val, g_pre, B, k, g_recon, ldg, x, ldx, K, dtype, dW_dec, ld_dec, dW_enc, ld_enc,
+                     db_enc, sq_dec, sq_enc, sq_b_enc, ws, nullptr, stream);
+}
+
+int cc_pairs_wgrad_add(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val,
+                       const float* g_pre, int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx,
+                       int64_t K, int dtype, void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc,
+                       float* sq_dec, float* sq_enc, float* sq_b_enc, float* ws, const int32_t* slot, int64_t d_pad,
+                       const void* aWd, int64_t lda_d, const void* aWe, int64_t lda_e, const void* ab, void* stream) {
+  const bool big = d_pad > INT32_MAX;
+  const PairAddend ad{slot, aWd, aWe, ab, lda_d, lda_e, (uint32_t)(d_pad < 0 ? 0 : (big ? 0xffffffffu : d_pad))};
+  return pairs_wgrad(perm, P, seg, h, val, g_pre, B, k, g_recon, ldg, x, ldx, K, dtype, dW_dec, ld_dec, dW_enc, ld_enc,
+                     db_enc, sq_dec, sq_enc, sq_b_enc, ws, &ad, stream);
 }
 
 }  // extern "C"

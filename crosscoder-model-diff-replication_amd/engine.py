@@ -212,12 +212,18 @@ class StepWorkspace:
         sparse (with topk, the Trainer's sparse step: forward_sparse / backward_sparse): the workspace owns the pairs
         (pair_idx, pair_val), their d_acts (pair_gpre, fp32), perm / seg and the grouping's and the list gradients'
         scratch; it allocates no g_pre, no g_pre column partials and no G2 split-K workspace, and the first three
-        segments of ws.sq take cc_pairs_wgrad's partials."""
+        segments of ws.sq take cc_pairs_wgrad's partials.
+        sparse with auxk ((k_aux,)): no aux halves; the aux problem is a dense one over the D
+        dead latents alone.  The workspace owns slot [h], the fp32 e^ and g_aux, the aux loss's parts and scalars,
+        was_dead, dead_count, the device's D, and -- flat, of a capacity that aux_reserve grows geometrically and never
+        shrinks, viewed per step by aux_views as [B][D_pad] / [D_pad][K] -- ids, acts_c (the selection runs in place and
+        leaves aux_c there), g_pre_c and its column partials, Wc_dec, the addends aWd / aWe / ab, the squared-sum
+        scratch nobody reads and the aux decode's split-K workspace."""
         f32 = torch.float32
         self.topk = topk
         self.sparse = bool(sparse)
-        if self.sparse and (topk is None or auxk is not None):
-            raise ValueError("a sparse workspace needs topk and excludes auxk")
+        if self.sparse and topk is None:
+            raise ValueError("a sparse workspace needs topk")
         self.batch_topk, self.bt_weighted = batch_topk if batch_topk is not None else (None, False)
         if topk is not None and batch_topk is not None:
             raise ValueError("topk and batch_topk exclude each other")
@@ -229,7 +235,8 @@ class StepWorkspace:
         elif auxk is not None:
             raise ValueError("auxk needs topk or batch_topk")
         self.k_aux = auxk[0] if auxk is not None else None
-        R = 2 * B if auxk is not None else B  # rows of the buffers that carry an aux half
+        # rows of the buffers that carry an aux half (a sparse workspace carries none: its aux problem is compact)
+        R = 2 * B if auxk is not None and not self.sparse else B
         K = n * d
         self.B, self.n, self.d, self.h, self.K, self.dtype = B, n, d, h, K, dtype
         E = lambda *s, dt=f32: torch.empty(*s, dtype=dt, device=device)  # noqa: E731
@@ -332,7 +339,19 @@ class StepWorkspace:
             self.group_ws = E(ops.pairs_group_ws_bytes(B, k, h), dt=torch.uint8)
             nwg = ops.pairs_wgrad_ws_floats(B * k, K)
             self.wgrad_ws = E(nwg) if nwg else None
-        if auxk is not None:
+        if auxk is not None and self.sparse:
+            self.ehat, self.g_aux = E(B, K), E(B, K, dt=dtype)
+            self.auxk_part = E(ops.auxk_part_floats(B, K))
+            self.auxk_scalars = torch.zeros(4, dtype=f32, device=device)
+            self.was_dead = torch.zeros(h, dtype=torch.uint8, device=device)
+            self.dead_count = torch.zeros(1, dtype=torch.int32, device=device)
+            self.slot = E(h, dt=torch.int32)
+            self.aux_count = torch.zeros(1, dtype=torch.int32, device=device)  # D as cc_dead_compact counted it
+            self.aux_cap = 0  # compact columns the flat buffers hold
+            self.aux_D = self.aux_Dp = 0  # the last active step's dead count (the host's) and D_pad
+            self.aux_dec_ws = None
+            self.aux_reserve(-(-h // AUX_CAP_FRACTION))
+        elif auxk is not None:
             # the aux halves, and the aux loss's partial slabs, scalars {auxk_loss, den, scale, valid}, the rows'
             # selected counts, the dead mask the step's selection used and the dead count after the step
             self.aux_acts, self.ehat, self.g_aux = self.acts_full[B:], self.recon_full[B:], self.g_recon_full[B:]
@@ -378,6 +397,46 @@ class StepWorkspace:
         self.x_next = None
         self.busy = None  # weakref to the token of an autograd graph whose backward still needs this workspace
 
+    def aux_reserve(self, D):
+        """A sparse AuxK workspace: room for D dead latents.  The capacity doubles until it holds aux_pad(D) (at most
+        the kernel h) and never shrinks; a torch allocation, for between steps.  -> whether it grew."""
+        need = min(aux_pad(D), self.h)
+        if need <= self.aux_cap:
+            return False
+        cap = max(self.aux_cap, AUX_GRANULE)
+        while cap < need:
+            cap *= 2
+        cap = self.aux_cap = min(cap, self.h)
+        B, K, dt, dev = self.B, self.K, self.dtype, self.x.device
+        E = lambda n, t=torch.float32: torch.empty(n, dtype=t, device=dev)  # noqa: E731
+        self._ids = E(cap, torch.int32)
+        self._acts_c, self._g_pre_c = E(B * cap, dt), E(B * cap, dt)
+        self._Wc_dec, self._aWd, self._aWe, self._ab = E(cap * K, dt), E(cap * K, dt), E(cap * K, dt), E(cap, dt)
+        self._gpre_colpart_c = E(ops.col_part_rows(B) * cap)
+        self._aux_sq = E(2 * ops.wgrad_parts(cap, K, dt) + ops.reduce_parts(cap))
+        return True
+
+    def aux_views(self, D):
+        """The step's views of the compact buffers for the host's dead count D (1 <= D, aux_pad(D) within the capacity):
+        ids [D_pad], acts_c = aux_c and g_pre_c [B][D_pad], Wc_dec, aWd, aWe [D_pad][K], ab [D_pad], the g_pre column
+        partials [col_part_rows(B)][D_pad].  ids and slot are rebuilt by every active step: nothing here is carried."""
+        Dp = min(aux_pad(D), self.h)
+        if Dp > self.aux_cap:
+            raise ValueError(f"the compact aux buffers hold {self.aux_cap} latents, {Dp} are needed: aux_reserve first")
+        B, K = self.B, self.K
+        self.aux_D, self.aux_Dp = int(D), Dp
+        self.ids = self._ids[:Dp]
+        self.acts_c = self.aux_c = self._acts_c[:B * Dp].view(B, Dp)
+        self.g_pre_c = self._g_pre_c[:B * Dp].view(B, Dp)
+        self.Wc_dec, self.aWd, self.aWe = (t[:Dp * K].view(Dp, K) for t in (self._Wc_dec, self._aWd, self._aWe))
+        self.ab = self._ab[:Dp]
+        cpr = ops.col_part_rows(B)
+        self.gpre_colpart_c = self._gpre_colpart_c[:cpr * Dp].view(cpr, Dp)
+        need = ops.decode_ws_floats(B, Dp, K, self.dtype)
+        if need and (self.aux_dec_ws is None or self.aux_dec_ws.numel() < need):
+            self.aux_dec_ws = torch.empty(need, dtype=torch.float32, device=self.x.device)
+        return Dp
+
     def next_slot(self):
         """Switch G1's partial slabs (acts_colpart, l0_part, colsum_acts) to the other slot (once per forward)."""
         self._slot ^= 1
@@ -385,6 +444,17 @@ class StepWorkspace:
 
     def sq_slice(self, i):
         return self.sq[self.sq_off[i]:self.sq_off[i + 1]]
+
+
+# The compact aux problem's latent extent D_pad is the dead count rounded up to AUX_GRANULE (a multiple of 8: the
+# kernels move 16-byte rows), and a sparse AuxK workspace starts with room for 1 / AUX_CAP_FRACTION of the latents
+# (DESIGN.md section 3.22).
+AUX_GRANULE = 8
+AUX_CAP_FRACTION = 32
+
+
+def aux_pad(D):
+    return max(1, -(-int(D) // AUX_GRANULE)) * AUX_GRANULE
 
 
 def transposed_wgrad(B, K, h, dtype):
@@ -561,17 +631,31 @@ def forward(ws, P, x_in, factor=None, grad_scale=None, want_grad=True, loss=True
             loss_finalize(ws)
 
 
-def forward_sparse(ws, P, x_in, factor=None, prep_tag=None):
+def forward_sparse(ws, P, x_in, factor=None, prep_tag=None, aux=None):
     """forward(finalize=False) of the sparse TopK step (a workspace built with sparse=True): prep
     and G1 as the dense TopK step, then the selection as k (value, latent) pairs per row with the same column-sum and
     count slabs (no dense masked write: ws.acts keeps G1's activations), the pairs grouped by latent (ws.perm, ws.seg),
     the plain event wait for the decoder-half Adam, the sparse G2 into ws.recon and the loss rows.  The caller forks
-    the loss tail (loss_finalize_beside, or loss_finalize on this stream)."""
+    the loss tail (loss_finalize_beside, or loss_finalize on this stream).
+    aux ((since_fired, h_real, dead_after, D), the Trainer's, a workspace built with auxk, D >= 1 the host's dead count
+    and within ws.aux_reserve): the dead set of since_fired is compacted (ws.ids, ws.slot), G1's activations of those
+    latents gathered into ws.acts_c and reduced in place to each row's min(k_aux, D) largest (ws.aux_c), and -- after
+    the wait for the decoder-half Adam -- their decoder rows gathered into ws.Wc_dec."""
     B, h, K = ws.B, ws.h, ws.K
     ws.next_slot()
     _take_or_prep(ws, x_in, factor, prep_tag)
     with _span("G1_encode"):
         ops.encode_fwd(ws.x, P.W_enc_hk, P.b_enc, ws.acts, True)
+    if aux is not None:
+        since_fired, h_real, dead_after, D = aux
+        Dp = ws.aux_views(D)
+        with _span("dead_compact"):
+            ops.dead_compact(since_fired, h_real, dead_after, ws.ids, ws.slot, ws.aux_count)
+        with _span("compact_cols"):
+            ops.compact_gather(ws.ids, h, acts=ws.acts, acts_c=ws.acts_c)
+        with _span("auxk_topk"):
+            # (ids ascends, so the tie order in the compact index is the tie order in the latent)
+            ops.topk_rows(ws.acts_c, Dp, min(ws.k_aux, int(D)), out=ws.acts_c)
     with _span("topk_pairs"):
         ops.topk_rows(ws.acts, h, ws.topk, out=None, idx_out=ws.pair_idx, val_out=ws.pair_val,
                       colsum_part=ws.acts_colpart, l0_part=ws.l0_part)
@@ -581,6 +665,9 @@ def forward_sparse(ws, P, x_in, factor=None, prep_tag=None):
     ops.reduce_rows(ws.acts_colpart, ws.acts_colpart.shape[0], h, out_f32=ws.colsum_acts)
     P.wait_pending()
     decoder_norms(ws, P)
+    if aux is not None:
+        with _span("compact_rows"):
+            ops.compact_gather(ws.ids, h, W=P.W_dec_hk, Wc=ws.Wc_dec)
     with _span("G2_decode_pairs"):
         ops.decode_pairs_partial(ws.pair_val, ws.pair_idx, P.W_dec_hk, K, h=h, recon=ws.recon)
     flush_norms(ws)
@@ -588,18 +675,55 @@ def forward_sparse(ws, P, x_in, factor=None, prep_tag=None):
     loss_rows(ws, P, 0, B)
 
 
-def backward_sparse(ws, P, G):
+def auxk_forward_sparse(ws, P, since_fired, h_real, dead_after, auxk_coeff, active, host=None):
+    """auxk_forward for the sparse step, after forward_sparse and before the loss tail is forked: the dead update
+    (always; the dead count also into word 10 of `host`), then -- active: forward_sparse(aux=...) ran -- the aux decode
+    e^ = aux_c . Wc_dec over the compact extent and the aux loss against the sparse step's fp32 ws.recon, with g_aux
+    (auxk_loss also into word 9 of `host`)."""
+    word = (lambda i: host.device_ptr.value + 4 * i) if host is not None else (lambda i: None)
+    with _span("dead_update"):
+        ops.dead_update(ws.colsum_acts, since_fired, h_real, ws.B, dead_after, ws.dead_count, was_dead=ws.was_dead,
+                        host_ptr=word(10))
+    ws.aux_active = bool(active)
+    if not active:
+        return
+    with _span("auxk_decode"):
+        ops.decode_partial(ws.aux_c, ws.Wc_dec, ws.ehat, ws.aux_dec_ws)
+    with _span("auxk_loss"):
+        ops.auxk_loss(ws.recon, P.b_dec_flat, ws.x, ws.ehat, ws.g_aux, ws.auxk_part, ws.auxk_scalars, auxk_coeff,
+                      host_ptr=word(9))
+
+
+def backward_sparse(ws, P, G, aux=False):
     """The sparse TopK step's backward, for l2 alone (l1_coeff = 0): d_acts at the pairs (the sampled dot products of
     g_recon with the selected decoder rows; a selected activation is > 0, so the straight-through mask is 1), the three
     list gradients with their squared-sum partials in one grouped launch pair, and b_dec's gradient from the loss's
-    column partials.  clip_and_adam then runs its clip_finalize over ws.sq."""
+    column partials.  clip_and_adam then runs its clip_finalize over ws.sq.
+    aux (an active AuxK step: auxk_forward_sparse left g_aux): the aux loss's gradients as a dense problem over the
+    compact extent -- G3 on the aux rows (no L1 term), G4 and G5 into the addends, the column sums of g_pre_c into ab,
+    their squared sums into scratch nobody reads -- which the list gradients' launch adds, row slot[j] to latent j, into
+    its fp32 sums before the one rounding (cc_pairs_wgrad_add).  Nothing of the aux loss reaches b_dec."""
     P.wait_pending()
     with _span("pairs_dacts"):
         ops.pairs_grad_values(ws.pair_idx, P.W_dec_hk, ws.g_recon, ws.n, ws.d, h=ws.h, total=ws.pair_gpre,
                               want_dot=False)
+    add = None
+    if aux:
+        Dp = ws.aux_Dp
+        nw = ops.wgrad_parts(Dp, ws.K, ws.dtype)
+        sq_d, sq_e, sq_b = ws._aux_sq[:nw], ws._aux_sq[nw:2 * nw], ws._aux_sq[2 * nw:2 * nw + ops.reduce_parts(Dp)]
+        with _span("G3_dacts_aux"):
+            ops.dacts_bwd(ws.g_aux, ws.Wc_dec, ws.aux_c, ws.tn, 0.0, ws.g_pre_c, colsum_part=ws.gpre_colpart_c)
+        with _span("G4_wgrad_dec_aux"):
+            ops.wgrad_dec(ws.aux_c, ws.g_aux, ws.Wc_dec, ws.inv_norms, ws.colsum_acts, 0.0, ws.aWd, sq_d, ws.n, ws.d)
+        with _span("G5_wgrad_enc_aux"):
+            ops.wgrad_enc(ws.g_pre_c, ws.x, ws.aWe, sq_e)
+        with _span("b_enc_grad_aux"):
+            ops.reduce_rows(ws.gpre_colpart_c, ws.gpre_colpart_c.shape[0], Dp, out_t=ws.ab, sq_part=sq_b)
+        add = (ws.slot, ws.aWd, ws.aWe, ws.ab)
     with _span("pairs_wgrad"):
         ops.pairs_wgrad(ws.perm, ws.seg, ws.pair_val, ws.pair_gpre, ws.g_recon, ws.x, ws.K, G.W_dec_hk, G.W_enc_hk,
-                        G.b_enc, ws.sq_slice(1), ws.sq_slice(0), ws.sq_slice(2), ws=ws.wgrad_ws)
+                        G.b_enc, ws.sq_slice(1), ws.sq_slice(0), ws.sq_slice(2), ws=ws.wgrad_ws, add=add)
     with _span("b_dec_grad"):
         ops.reduce_rows(loss_colpart(ws), ws.loss_col_rows, ws.K, out_t=G.b_dec_flat, sq_part=ws.sq_slice(3))
     ws.clip_ready = False

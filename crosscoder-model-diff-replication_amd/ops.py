@@ -1042,13 +1042,15 @@ def pairs_wgrad_parts(h):
     return int(lib().cc_pairs_wgrad_parts(h))
 
 
-def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq_dec, sq_enc, sq_b_enc, ws=None):
+def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq_dec, sq_enc, sq_b_enc, ws=None,
+                add=None):
     """The sparse step's weight gradients from the pairs grouped by latent (cc_pairs_wgrad): per latent j and its list
     in perm's order, dW_dec[j] = sum val * g_recon[row], dW_enc[j] = sum p * x[row], db_enc[j] = sum p with p = g_pre
     rounded to the dtype -- pairs_grad_decoder's order for all three, rounded once -- plus the squared sums of the
     stored values, pairs_wgrad_parts(h) fp32 partials per parameter.  val [B, k] (bf16 / fp32) and g_pre fp32 [B, k],
     contiguous; g_recon, x [B, >= K] and dW_dec, dW_enc [h, >= K] of val's dtype (pitches kept); db_enc [h] of it; ws:
-    fp32, at least pairs_wgrad_ws_floats(len(perm), K) elements (allocated when None)."""
+    fp32, at least pairs_wgrad_ws_floats(len(perm), K) elements (allocated when None).
+    add (pairs_wgrad_add's (slot, aWd, aWe, ab)): the compact addends, through cc_pairs_wgrad_add."""
     B, k = _pairs_val(val)
     dt, dev = val.dtype, val.device
     P, h = _grouped(perm, seg, dev)
@@ -1067,9 +1069,29 @@ def pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq
     stream = _stream(val)
     if ws is None and need:
         ws = torch.empty(pairs_wgrad_ws_floats(P, K), dtype=torch.float32, device=dev)
-    check(lib().cc_pairs_wgrad(_ptr(perm), P, _ptr(seg), h, _ptr(val), _ptr(g_pre), B, k, pg, ldg, px, ldx, K,
-                               dtype_code(dt), pd, ldd, pe, lde, _ptr(db_enc), _ptr(sq_dec), _ptr(sq_enc),
-                               _ptr(sq_b_enc), _ptr(ws), stream))
+    args = (_ptr(perm), P, _ptr(seg), h, _ptr(val), _ptr(g_pre), B, k, pg, ldg, px, ldx, K, dtype_code(dt), pd, ldd, pe,
+            lde, _ptr(db_enc), _ptr(sq_dec), _ptr(sq_enc), _ptr(sq_b_enc), _ptr(ws))
+    if add is None:
+        check(lib().cc_pairs_wgrad(*args, stream))
+        return
+    slot, aWd, aWe, ab = add
+    _dense(slot, torch.int32, (h,), dev, "slot")
+    if slot is None or aWd is None or aWe is None or ab is None:
+        raise ValueError("slot and the three addends are all needed")
+    Dp = aWd.shape[0] if aWd.dim() == 2 else 0
+    (pad, lad), (pae, lae) = _rows(aWd, Dp, K, dt, dev, "aWd"), _rows(aWe, Dp, K, dt, dev, "aWe")
+    _dense(ab, dt, (Dp,), dev, "ab")
+    check(lib().cc_pairs_wgrad_add(*args, _ptr(slot), Dp, pad, lad, pae, lae, _ptr(ab), stream))
+
+
+def pairs_wgrad_add(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq_dec, sq_enc, sq_b_enc, slot, aWd,
+                    aWe, ab, ws=None):
+    """pairs_wgrad with the compact addends of the AuxK loss's dead set (cc_pairs_wgrad_add): for a latent j with
+    s = slot[j] >= 0 (int32 [h]; ops.dead_compact's), rows s of aWd, aWe [D_pad, >= K] and element s of ab [D_pad]
+    (val's dtype) are added to the fp32 sums of dW_dec[j], dW_enc[j] and db_enc[j] before their one rounding.  The
+    squared sums are those of the stored values."""
+    pairs_wgrad(perm, seg, val, g_pre, g_recon, x, K, dW_dec, dW_enc, db_enc, sq_dec, sq_enc, sq_b_enc, ws=ws,
+                add=(slot, aWd, aWe, ab))
 
 
 # ---------------------------------------------------------------- BatchTopK (one selection over the whole batch)
@@ -1208,6 +1230,52 @@ def add_rows(dst, src):
     rows, ld = _rows_ld(dst, "dst")
     _like(src, dst, "src", "dst")
     check(lib().cc_add_rows(_ptr(dst), _ptr(src), rows, dst.shape[1], ld, dtype_code(dst.dtype), _stream(dst)))
+
+
+# ---------------------------------------------------------------- the compacted dead set (the sparse step's AuxK)
+def dead_compact(since_fired, h_real, dead_after, ids, slot, count):
+    """The dead latents of since_fired [h] (int64; dead: >= dead_after, latents >= h_real never) in ascending order
+    (cc_dead_compact): ids int32 [D_pad] (D_pad a multiple of 8) <- the c-th dead latent, -1 from their number D on;
+    slot int32 [h] <- every latent's compact index or -1; count (int32 [1]) <- D.  Dead latents from D_pad on are
+    dropped."""
+    h, dev = since_fired.numel(), since_fired.device
+    _dense(since_fired, torch.int64, (h,), dev, "since_fired")
+    _dense(slot, torch.int32, (h,), dev, "slot")
+    if ids is None or ids.dtype != torch.int32 or ids.dim() != 1 or ids.device != dev or not ids.is_contiguous():
+        raise ValueError(f"ids must be a contiguous int32 vector on {dev}")
+    _mult8(ids.numel(), "len(ids)")
+    if slot is None or count is None or count.dtype != torch.int32 or count.numel() != 1 or count.device != dev:
+        raise ValueError(f"slot is needed, and count must be an int32 tensor of one element on {dev}")
+    check(lib().cc_dead_compact(_ptr(since_fired), h, int(h_real), int(dead_after), _ptr(ids), ids.numel(), _ptr(slot),
+                                _ptr(count), _stream(since_fired)))
+
+
+def compact_gather(ids, h, W=None, Wc=None, acts=None, acts_c=None):
+    """Bit copies through ids (int32 [D_pad], ops.dead_compact's) of latents below h (cc_compact_gather): rows,
+    Wc[c] = W[ids[c]] for W [>= h, >= K] and Wc [D_pad, K]; columns, acts_c[r][c] = acts[r][ids[c]] for acts
+    [B, >= h] (rows contiguous) and acts_c [B, D_pad] contiguous.  An ids[c] < 0 gives a +0 row / column.  Either
+    pair may be left out."""
+    dev = ids.device
+    Dp = _mult8(ids.numel(), "len(ids)")
+    if ids.dtype != torch.int32 or ids.dim() != 1 or not ids.is_contiguous():
+        raise ValueError("ids must be a contiguous int32 vector")
+    if (W is None) != (Wc is None) or (acts is None) != (acts_c is None) or (W is None and acts is None):
+        raise ValueError("W goes with Wc and acts with acts_c; one pair at least")
+    _int_at_least(h, "h")
+    pw = pc = pa = po = None
+    ldw = ldc = K = lda = B = 0
+    dt = (W if W is not None else acts).dtype
+    if W is not None:
+        K = _mult8(Wc.shape[1] if Wc.dim() == 2 else 0, "Wc's columns")
+        pw, ldw, _ = _decoder(W, K, dt, dev, h)
+        pc, ldc = _rows(Wc, Dp, K, dt, dev, "Wc")
+    if acts is not None:
+        B, lda = _rows_ld(acts, "acts")
+        if acts.shape[1] < h or acts.device != dev:
+            raise ValueError(f"acts must be [B, >= {h}] on {dev}")
+        _dense(acts_c, dt, (B, Dp), dev, "acts_c")
+        pa, po = _ptr(acts), _ptr(acts_c)
+    check(lib().cc_compact_gather(_ptr(ids), Dp, h, pw, ldw, K, pc, ldc, pa, lda, B, po, dtype_code(dt), _stream(ids)))
 
 
 # ---------------------------------------------------------------- JumpReLU (one learned threshold per latent)

@@ -13,13 +13,15 @@ cfg["resample_every"] = N re-seeds the dead latents after every N-th step (dead-
 3.18; `Trainer.resample_dead_latents` is the same between steps of the caller's choosing).
 cfg["sparse_step"] = True (TopK crosscoders, l1_coeff 0) runs the step's decode and backward on the k (value, latent)
 pairs per row instead of the masked dense activations; `Trainer.sparse_step` says which ran.
+cfg["auxk_compact"] = True serves the AuxK loss under the sparse step, its GEMMs over the compacted dead set alone
+(DESIGN.md section 3.22).
 """
 import torch
 import tqdm
 
 from . import _hip, engine
 from .buffer import Buffer
-from .crosscoder import CrossCoder, master_weights_of, sparse_step_of
+from .crosscoder import CrossCoder, auxk_compact_of, master_weights_of, sparse_step_of
 from .resample import LatentResampler
 
 RESAMPLE_ROWS = 819200  # cfg["resample_rows"]'s default: the pool of "Towards Monosemanticity"'s neuron resampling
@@ -257,14 +259,17 @@ class Trainer:
         self._resampler = None
         # the sparse TopK step (crosscoder.sparse_step_of): what it does not serve is refused here, not run densely
         self.sparse_step = sparse_step_of(cfg)
+        # the AuxK loss of the sparse step: the aux GEMMs on the compacted dead set
+        self.auxk_compact = auxk_compact_of(cfg)
         self._sparse_ws = None  # its workspace, the Trainer's own: the crosscoder's serves get_losses' dense autograd
         if self.sparse_step:
             why = None
             if cfg["l1_coeff"] != 0:
                 why = ("cfg['l1_coeff'] != 0: TopK replaces the L1 penalty, and the L1 term's dense dW_dec part is not "
                        "built for the sparse step")
-            elif self.auxk is not None:
-                why = "cfg['auxk_coeff'] > 0: the AuxK loss on pairs is not built"
+            elif self.auxk is not None and not self.auxk_compact:
+                why = ("cfg['auxk_coeff'] > 0: the AuxK loss on pairs is not built; cfg['auxk_compact'] = True serves "
+                       "it with the aux GEMMs on the compacted dead set")
             elif self.resample is not None:
                 why = "cfg['resample_every']: resampling under the sparse step is not built"
             elif latent_stats is not None:
@@ -324,7 +329,9 @@ class Trainer:
     def auxk_state(self):
         """The last step's AuxK state (synchronises): aux_acts ([batch, dict_size], a view of the step's aux
         activations; zeros when the step issued no aux launches), dead (bool [dict_size], the dead set the step
-        used), den, auxk_loss and dead_latents (the dead count after the step)."""
+        used), den, auxk_loss and dead_latents (the dead count after the step).  The sparse step (cfg["auxk_compact"])
+        scatters aux_acts from its compact form and adds dead_ids (int64, the dead latents in the compact order) and
+        compact_count (the dead count cc_dead_compact found on the device: the host's, which sized the step)."""
         ws = self._last_ws
         if self.auxk is None or ws is None:
             raise ValueError("auxk_state(): no AuxK step has run")
@@ -332,6 +339,19 @@ class Trainer:
         hr = self.crosscoder.d_hidden
         sc = ws.auxk_scalars.cpu()
         active = ws.aux_active
+        if ws.sparse:
+            # the compact form scattered to [batch, dict_size] (plain torch: not the hot path); dead_ids: the dead set
+            # in the compact order, ascending
+            aux = torch.zeros(ws.B, ws.h, dtype=ws.dtype, device=ws.x.device)
+            ids = torch.zeros(0, dtype=torch.int64, device=ws.x.device)
+            if active:
+                ids = ws.ids[:min(ws.aux_D, ws.aux_Dp)].long()
+                aux[:, ids] = ws.aux_c[:, :ids.numel()]
+            return {"aux_acts": aux[:, :hr], "dead": ws.was_dead[:hr].bool(),
+                    "row_count": (aux > 0).sum(1, dtype=torch.int32) if active else None,
+                    "den": float(sc[1]) if active else 0.0, "auxk_loss": float(sc[0]) if active else 0.0,
+                    "dead_latents": int(ws.dead_count), "dead_ids": ids,
+                    "compact_count": int(ws.aux_count) if active else 0}
         return {"aux_acts": ws.aux_acts[:, :hr] if active else torch.zeros_like(ws.aux_acts[:, :hr]),
                 "dead": ws.was_dead[:hr].bool(), "row_count": ws.aux_row_count if active else None,
                 "den": float(sc[1]) if active else 0.0, "auxk_loss": float(sc[0]) if active else 0.0,
@@ -353,8 +373,8 @@ class Trainer:
         opt = self.optimizer
         side = self._side_stream()
         if self.sparse_step:
-            ws = self._launch_sparse_step(raw, factor if normalize else None, tag, P, side, host, seq)
-            return self._launch_adam(ws, P, side, normalize, self.get_l1_coeff(), None, False)
+            ws, aux_on = self._launch_sparse_step(raw, factor if normalize else None, tag, P, side, host, seq)
+            return self._launch_adam(ws, P, side, normalize, self.get_l1_coeff(), None, aux_on)
         ws = cc._workspace(raw.shape[0], step=True)
         # prep, G1, G2 + the loss rows (one pass where decode_loss_t serves the shape)
         # (BatchTopK: the selection's last launch folds the step's threshold score T into the crosscoder's inference
@@ -418,18 +438,31 @@ class Trainer:
         cc, ws = self.crosscoder, self._sparse_ws
         if ws is None or ws.B != B or ws.x.device != P.data.device:
             ws = self._sparse_ws = engine.StepWorkspace(B, cc.n_models, cc._dp, cc._hp, cc.dtype, P.data.device,
-                                                        topk=cc.k, sparse=True)
+                                                        topk=cc.k, sparse=True,
+                                                        auxk=(self.auxk[1],) if self.auxk is not None else None)
         return ws
 
     def _launch_sparse_step(self, raw, factor, tag, P, side, host, seq):
         """_launch_step's forward and backward for cfg["sparse_step"] (engine.forward_sparse / backward_sparse): no launch
         of it waits in its kernel, so the step has no abort word, and the loss tail runs beside d_acts on the side
-        stream.  -> the workspace, for _launch_adam."""
+        stream.  With cfg["auxk_compact"]: the dead update after the loss rows and, while the host's dead count is not
+        0, the aux problem on the compacted dead set; the loss tail is forked after both, so
+        its sequence word publishes words 9 and 10 too.  -> the workspace and whether the aux launches ran, for
+        _launch_adam."""
         ws = self._sparse_workspace(raw.shape[0], P)
-        engine.forward_sparse(ws, P, raw, factor, prep_tag=tag)
+        aux_on = self.auxk is not None and self._dead_count > 0
+        aux = None
+        if aux_on:
+            # (the capacity follows the dead count the host already holds: an allocation between steps, no sync)
+            ws.aux_reserve(self._dead_count)
+            aux = (self._since_fired(), self.crosscoder.d_hidden, self.auxk[2], self._dead_count)
+        engine.forward_sparse(ws, P, raw, factor, prep_tag=tag, aux=aux)
+        if self.auxk is not None:
+            engine.auxk_forward_sparse(ws, P, self._since_fired(), self.crosscoder.d_hidden, self.auxk[2], self.auxk[0],
+                                       aux_on, host=host)
         engine.loss_finalize_beside(ws, side, host=host, seq=seq)
-        engine.backward_sparse(ws, P, self.optimizer.grads)
-        return ws
+        engine.backward_sparse(ws, P, self.optimizer.grads, aux=aux_on)
+        return ws, aux_on
 
     def _side_stream(self):
         # the decoder half of Adam (+ the next step's decoder norms / W_dec^T) runs here, beside the

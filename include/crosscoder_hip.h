@@ -893,6 +893,41 @@ int cc_pairs_wgrad(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h
                    void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc, float* sq_dec,
                    float* sq_enc, float* sq_b_enc, float* ws, void* stream);
 
+/* ---- the compacted dead set of the sparse step's AuxK loss (csrc/auxk_compact.hip, csrc/sparse_step.hip) ----
+ * cc_dead_compact: the dead latents of since_fired [h] (int64; dead: since_fired >= dead_after, latents >= h_real
+ * never) in ascending latent order: ids[c] (int32 [d_pad]) is the c-th dead latent for c < D and -1 from D on,
+ * slot[j] (int32 [h]) the compact index of latent j or -1, *count (uint32) = D.  Dead latents from d_pad on are
+ * dropped (slot -1): *count > d_pad says so.  One launch of one workgroup: a scan, no atomics, no arrival order.
+ * Errors in this order: CC_ERR_SHAPE (h < 1, h_real outside 0..h, d_pad < 8 or not a multiple of 8), CC_ERR_NULL,
+ * CC_ERR_TOO_LARGE (h or d_pad > 2^17), CC_ERR_ALIGN (8 bytes: since_fired; 4: ids, slot, count).
+ *
+ * cc_compact_gather: bit copies through ids [d_pad] -- either group may be left out (both of its pointers NULL):
+ *   rows     Wc[c][0 .. K) = W[ids[c]][0 .. K)          W [h][ldw], Wc [d_pad][ldc] (dtype), 16-byte vectors
+ *   columns  acts_c[r][c]  = acts[r][ids[c]]            acts [B][lda], acts_c [B][d_pad] (dtype, dense)
+ * An ids[c] outside [0, h) gives a +0 row / column.  One launch per group on `stream` (columns first).
+ * Errors in this order: CC_ERR_SHAPE (d_pad < 8 or not a multiple of 8, h < 1; rows: K < 8, K % 8 != 0, a pitch < K;
+ * columns: B < 1, lda < h), CC_ERR_NULL (ids, no group, half a group, a group in place), CC_ERR_DTYPE,
+ * CC_ERR_TOO_LARGE (h or K > 2^31 - 1, d_pad > 2^17, B > 2^20), CC_ERR_ALIGN (16 bytes: W, Wc, their pitches, acts_c;
+ * 4: ids; acts: its element).
+ *
+ * cc_pairs_wgrad_add: cc_pairs_wgrad with three addends, given together or all NULL (then it is cc_pairs_wgrad): for a
+ * latent j with s = slot[j] in [0, d_pad), float(aWd[s][c]), float(aWe[s][c]) and float(ab[s]) are added to the fp32
+ * sums of dW_dec[j][c], dW_enc[j][c] and db_enc[j] after the list's and before the one rounding; any other slot adds
+ * nothing.  slot int32 [h]; aWd [d_pad][lda_d], aWe [d_pad][lda_e] and ab [d_pad] in the dtype.  The squared sums are
+ * those of the stored values, in cc_pairs_wgrad's order.
+ * Errors: cc_pairs_wgrad's, with -- CC_ERR_SHAPE: d_pad < 1 or an addend pitch < K; CC_ERR_NULL: some addends without
+ * the others; CC_ERR_TOO_LARGE: d_pad > 2^31 - 1; CC_ERR_ALIGN, after cc_pairs_wgrad's own: aWd, aWe and their pitches
+ * 16 bytes, slot 4, ab its element. */
+int cc_dead_compact(const int64_t* since_fired, int64_t h, int64_t h_real, int64_t dead_after, int32_t* ids,
+                    int64_t d_pad, int32_t* slot, uint32_t* count, void* stream);
+int cc_compact_gather(const int32_t* ids, int64_t d_pad, int64_t h, const void* W, int64_t ldw, int64_t K, void* Wc,
+                      int64_t ldc, const void* acts, int64_t lda, int64_t B, void* acts_c, int dtype, void* stream);
+int cc_pairs_wgrad_add(const int32_t* perm, int64_t P, const int64_t* seg, int64_t h, const void* val,
+                       const float* g_pre, int64_t B, int k, const void* g_recon, int64_t ldg, const void* x, int64_t ldx,
+                       int64_t K, int dtype, void* dW_dec, int64_t ld_dec, void* dW_enc, int64_t ld_enc, void* db_enc,
+                       float* sq_dec, float* sq_enc, float* sq_b_enc, float* ws, const int32_t* slot, int64_t d_pad,
+                       const void* aWd, int64_t lda_d, const void* aWe, int64_t lda_e, const void* ab, void* stream);
+
 #pragma GCC visibility pop
 
 #ifdef __cplusplus
